@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the hot-path benchmark (driver contract: one JSON line on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ntt|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ntt|c5] [--dump-outputs DIR]
 
 Launch.  With --gpus N > 1 and no torch.distributed environment, bench.py starts N ranks itself
 (`python -m torch.distributed.run`, one process per GPU, as a CHILD process and before this process touches the GPU);
@@ -29,6 +29,16 @@ Also on the line:
   cpu_baseline  -- the C oracle (oracle/oracle.c: the reference's recursive algorithm) on a bounded sample of the same
                    workload, rank 0 at N = 1 only.
   extra         -- FRI commits, Merkle commit of 2^24 leaves, LDE, whole STARK proofs.
+
+--dump-outputs DIR (rank 0) writes what the timed path computed in its last timed step as DIR/<name>.npy, float64, at most
+64 MB in all; the inputs are seeded, so two builds run with the same arguments can be compared array for array.  Field
+elements and proof bytes are written as their big-endian 32-bit words (exact in float64), one row per element or proof:
+  ntt  ntt_output [rows, 8]        y = invNTT(NTT(x)) of the last step: every element of the [batch][n] output, or a fixed
+                                   seeded sample of them when they would exceed the budget
+       ntt_output_index [rows]     the flat index (vector * n + i) of each row
+  c5   proof_headers [units, 16]   m_root | l_root of every proof of the batch
+       proofs [rows, bytes / 4]    whole flat proofs of rank 0's units (all of them, or a fixed seeded sample)
+       proofs_unit [rows]          the unit of each row
 """
 import argparse
 import datetime
@@ -50,6 +60,37 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 
 def root_of(n):
     return pow(7, (P - 1) // n, P)
+
+
+DUMP_ROWS_BYTES = 48 << 20  # the sampled rows of one --dump-outputs; with the small index / header arrays the dump stays under 64 MB
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_rows(total, row_bytes, seed):
+    """Sorted indices of the rows --dump-outputs writes: all of them when they fit DUMP_ROWS_BYTES, else a fixed seeded sample."""
+    import numpy as np
+    k = DUMP_ROWS_BYTES // row_bytes
+    if total <= k:
+        return np.arange(total)
+    return np.sort(np.random.default_rng(seed).choice(total, k, replace=False))
+
+
+def words(raw):
+    """Big-endian 32-bit words of wire-form bytes (canonical field elements, digests, flat proofs) as float64 (exact)."""
+    import numpy as np
+    return np.frombuffer(raw, dtype=">u4").astype(np.float64)
+
+
+def write_dump(out_dir, arrays):
+    """DIR/<name>.npy for every array; returns {name: shape} for the result line."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 class Dev:
@@ -673,11 +714,15 @@ def main():
                     "(the launcher must exit non-zero, not hang)")
     ap.add_argument("--dry-run", action="store_true", help="CPU tests: launcher, sharding and gather only -- no GPU work, "
                     "value = null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step "
+                    "to DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.workload == "ntt" else 2
     if args.warmup is None:
         args.warmup = 3 if args.workload == "ntt" else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.units is None:
         args.units = 16 if args.quick else 512
     if args.logsteps is None:
@@ -760,8 +805,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
         return bool(int(t.item()))
 
-    def run_c5(steps_k, warm_k):
-        """K timed steps of the many-proof workload; returns the result dict (rank-independent fields agree on all ranks)."""
+    def run_c5(steps_k, warm_k, dump_dir=None):
+        """K timed steps of the many-proof workload; returns the result dict (rank-independent fields agree on all ranks).
+        dump_dir: rank 0 writes the last timed step's proofs there (--dump-outputs)."""
         steps = 1 << args.logsteps
         mine = shard(args.units, rank, world)
         # proofs per batched launch: --chunk, but never so many that one of the contexts stays idle (a rank of the 8-GPU run holds 64
@@ -783,6 +829,13 @@ def main():
         fence()
         dt_own = time.perf_counter() - t0
         dt = max_over_ranks(dt_own)
+        dump = None
+        if dump_dir and rank == 0:  # read now: the legs below prove the same units again into the same buffer
+            import numpy as np
+            sel = dump_rows(len(mine), 2 * sh.plen, 0xC5)
+            dump = {"proof_headers": words(b"".join(heads)).reshape(-1, 16),
+                    "proofs": np.stack([words(sh.proof(int(i))) for i in sel]),
+                    "proofs_unit": np.asarray([mine[i] for i in sel], dtype=np.float64)}
         # the same steps with every proof DELIVERED: the flat proofs of each launch sequence are copied into page-locked host memory
         # on the contexts' copy streams while the next sequence is being proved (STARK.mk_proof returns its proof, stark.py:233-279);
         # a step ends when the last byte has arrived.  Reported beside the on-device figure, never as `value`.
@@ -831,12 +884,14 @@ def main():
                                      "timed regions (sh_dev_fill_mimc_units: one sequential x <- x^3 + k chain of 2^16 steps per unit)"},
                "per_rank_ms_per_step": per_rank(dt_own / steps_k * 1e3),
                "check": {"ok": ok, "rank0": chk}}
+        if dump is not None:
+            res["dump_outputs"] = write_dump(dump_dir, dump)
         sh.close()
         return res
 
     # =================================================================================================================
     if args.workload == "c5":
-        res = run_c5(args.steps, args.warmup)
+        res = run_c5(args.steps, args.warmup, args.dump_outputs)
         steps = 1 << args.logsteps
         n = steps * 8
         # SURVEY 8(d) gives per-unit bytes for the NTT (64 B per element per transform) and the FRI commit (203 B per domain
@@ -863,6 +918,8 @@ def main():
                          "note": "SURVEY 8(d) bytes of the proof's transforms and FRI commit only (the quotient, packed-leaf and "
                                  "combination kernels have no 8(d) figure); integer-VALU / BLAKE2s-ALU bound, not HBM bound"},
         }
+        if "dump_outputs" in res:
+            line["dump_outputs"] = res.pop("dump_outputs")
         if rank == 0 and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_c5(steps, dev=dev)
         if rank == 0:
@@ -903,11 +960,18 @@ def main():
     CH = min(n * B, 1 << 20)
     a, b = ctypes.create_string_buffer(32 * CH), ctypes.create_string_buffer(32 * CH)
     roundtrip_ok = True
+    dump_idx = None
+    if args.dump_outputs and rank == 0:  # the rows of y the dump keeps, picked from the chunks this check reads anyway
+        import numpy as np
+        dump_idx, dump_parts = dump_rows(n * B, 64, 0x5eed), []
     for off in range(0, n * B, CH):
         k = min(CH, n * B - off)  # the last chunk of a batch that is not a multiple of 2^20 elements is shorter
         dev.ck(L.sh_dev_to_wire(ctx, ctypes.c_void_p(dx.value + 32 * off), a, k), "dl")
         dev.ck(L.sh_dev_to_wire(ctx, ctypes.c_void_p(dy.value + 32 * off), b, k), "dl")
         roundtrip_ok = roundtrip_ok and a.raw[:32 * k] == b.raw[:32 * k]
+        if dump_idx is not None:
+            lo, hi = np.searchsorted(dump_idx, [off, off + k])
+            dump_parts.append(np.frombuffer(b, dtype=">u4", count=8 * k).reshape(k, 8)[dump_idx[lo:hi] - off].astype(np.float64))
     dev.ck(L.sh_dev_ntt(ctx, dx, dy, n, B, w, 0), "ntt")
     h = hashlib.sha256()
     for off in range(0, n, CH):  # vector 0
@@ -980,6 +1044,9 @@ def main():
                      "note": "achieved / peak / frac are the algorithmic HBM bytes of SURVEY 8(d) against the HBM peak, as the metric "
                              "asks; the kernel is bound by integer-VALU issue: see roofline_alu (DESIGN.md section 5)"},
     }
+    if dump_idx is not None:
+        line["dump_outputs"] = write_dump(args.dump_outputs, {"ntt_output": np.concatenate(dump_parts),
+                                                              "ntt_output_index": dump_idx.astype(np.float64)})
     if lane_instr:
         # the roof that binds: VALU lane-instructions the transform executes (committed counters of this command) x elements/s
         # of THIS run, against the wall-clock issue peak of the pass's own instruction mix (tools/alu_mix_bench, run below)

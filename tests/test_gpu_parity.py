@@ -1260,6 +1260,44 @@ def test_plan_cache_is_lru_with_a_byte_budget(sa, oracle):
         L.sh_ctx_destroy(ctx)
 
 
+@pytest.mark.parametrize("workload", ["ntt", "c5"])
+def test_bench_dump_outputs(sa, workload, tmp_path):
+    """bench.py --dump-outputs DIR writes what the timed steps computed, and --steps sets their number.  ntt: the output
+    y = invNTT(NTT(x)) of both vectors is the seeded input, row for row (x_i = BLAKE2s(seed_le64 || i_le64) mod p, what
+    sh_dev_fill_seeded writes); c5: every proof of the --quick batch, whose bytes hash to the digest the bench's own check took
+    of the device buffer, and whose first 64 bytes are the dumped headers."""
+    import json, subprocess, sys
+    import numpy as np
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    args = ["--quick", "--no-cpu-baseline", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    if workload == "ntt":
+        args += ["--logn", "14", "--batch", "2", "--no-extras", "--no-c5", "--no-single", "--no-alu-peak"]
+    else:
+        args += ["--workload", "c5"]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=600,
+                         env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    got = {f[:-len(".npy")]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {k: list(v.shape) for k, v in got.items()} == line["dump_outputs"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    if workload == "ntt":
+        total = 2 << 14  # two vectors of 2^14 points
+        assert got["ntt_output_index"].tolist() == list(range(total))
+        want = b"".join((int.from_bytes(hashlib.blake2s((0x5eed).to_bytes(8, "little") + i.to_bytes(8, "little")).digest(), "big")
+                         % P).to_bytes(32, "big") for i in range(total))
+        assert got["ntt_output"].astype(">u4").tobytes() == want
+    else:
+        assert got["proofs_unit"].tolist() == list(range(16)) and got["proof_headers"].shape == (16, 16)
+        proofs = got["proofs"].astype(">u4")
+        assert hashlib.sha256(proofs.tobytes()).hexdigest() == line["c5"]["check"]["rank0"]["all_proofs_sha256"]
+        assert np.array_equal(proofs[:, :16], got["proof_headers"])
+
+
 @pytest.mark.parametrize("args", [["--workload", "c5", "--quick"],
                                   ["--quick", "--steps", "2", "--warmup", "1", "--no-extras", "--logn", "14"]])
 def test_bench_two_ranks_share_this_gpu(sa, args):

@@ -78,6 +78,27 @@ def test_bench_spawns_its_own_ranks():
     assert one["n_gpus"] == 1 and one["units_per_rank"] == [5]
 
 
+def test_bench_dump_rows_fixed_and_bounded():
+    """--dump-outputs: the sampled rows are the same from run to run, distinct and sorted, and the dump of the default 2^24-point
+    shape stays under 64 MB; an output that fits is written whole.  --steps below 1 is refused."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    idx = bench.dump_rows(1 << 24, 64, 0x5eed)
+    assert np.array_equal(idx, bench.dump_rows(1 << 24, 64, 0x5eed))
+    assert len(idx) > 0 and np.all(np.diff(idx) > 0) and idx[-1] < 1 << 24
+    assert len(idx) * (64 + 8) <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(bench.dump_rows(1 << 14, 64, 0x5eed), np.arange(1 << 14))
+    p = 2**256 - 2**32 * 351 + 1
+    assert bench.words((p - 1).to_bytes(32, "big")).tolist() == [((p - 1) >> (32 * (7 - i))) & 0xFFFFFFFF for i in range(8)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], capture_output=True,
+                         text=True, timeout=120, env=env)
+    assert out.returncode == 2 and "--steps must be at least 1" in out.stderr
+
+
 def test_bench_eight_ranks_dry_run():
     """The shape of the driver's 8-GPU run, on CPU: eight ranks over gloo, config 5's 512 units sharded 64 per rank, the header
     all_gather and the all_gather_object of the rank records (what a real run reports under `ranks`)."""
