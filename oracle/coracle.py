@@ -41,6 +41,16 @@ def lib():
         L.or_lde.restype = i32
         L.or_field_op.argtypes = [i32, u8p, u8p, u64, u8p]
         L.or_field_op.restype = None
+        L.or_stark_c.argtypes = [u8p, u32, u64, u32, u32, u8p, u8p, u32, u8p]
+        L.or_stark_c.restype = None
+        L.or_stark_d.argtypes = [u8p, u64, u64, u8p, u8p]
+        L.or_stark_d.restype = i32
+        L.or_div_linear.argtypes = [u8p, u64, u8p, u8p]
+        L.or_div_linear.restype = None
+        L.or_lincomb.argtypes = [u8p, u32, u64, u8p, u8p]
+        L.or_lincomb.restype = None
+        L.or_merkelize_columns.argtypes = [u8p, u32, u64, u8p]
+        L.or_merkelize_columns.restype = None
         _LIB = L
     return _LIB
 

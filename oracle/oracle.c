@@ -573,3 +573,109 @@ void or_field_op(int op, const uint8_t* a, const uint8_t* b, uint64_t n, uint8_t
     fe_to_wire(&r, out + 32 * i);
   }
 }
+
+/* ---- starks/stark.py:27-279 in O(n log n): the pieces of oracle/fastoracle.py that touch every point ------------ */
+/* The reference builds C, D and B with schoolbook products and long division (O(n^2)); these are the same polynomials,
+ * exactly, from O(n) passes between the NTTs above. */
+
+/* stark.py:38-57 on the domain x_i = g2^i (i < n): out_i = P_j(g1 x_i) - step_j(P_1(x_i) .. P_W(x_i)), with
+ * P_j(g1 x_i) = vals[j][(i + ext) mod n].  vals: [width][n]; terms: coefs[t] (32 B), exps[t][width] (one byte per
+ * variable).  The step polynomial is evaluated term by term as multivariate_polynomial.py:329-338 does (each power by
+ * repeated multiplication); the value is the residue of C_j there. */
+void or_stark_c(const uint8_t* vals, uint32_t width, uint64_t n, uint32_t ext, uint32_t j, const uint8_t* coefs,
+                const uint8_t* exps, uint32_t nterms, uint8_t* out) {
+  fe* cf = (fe*)malloc(sizeof(fe) * (nterms ? nterms : 1));
+  fe* v = (fe*)malloc(sizeof(fe) * width);
+  for (uint32_t t = 0; t < nterms; ++t) cf[t] = fe_from_wire(coefs + 32 * t);
+  for (uint64_t i = 0; i < n; ++i) {
+    for (uint32_t d = 0; d < width; ++d) v[d] = fe_from_wire(vals + 32 * (d * n + i));
+    fe y = fe_u64(0);
+    for (uint32_t t = 0; t < nterms; ++t) {
+      fe prod = fe_u64(1);
+      for (uint32_t d = 0; d < width; ++d)
+        for (unsigned e = 0; e < exps[t * width + d]; ++e) prod = fe_mul(&prod, &v[d]);
+      prod = fe_mul(&prod, &cf[t]);
+      y = fe_add(&y, &prod);
+    }
+    fe nxt = fe_from_wire(vals + 32 * (j * n + (i + ext) % n));
+    fe r = fe_sub(&nxt, &y);
+    fe_to_wire(&r, out + 32 * i);
+  }
+  free(v);
+  free(cf);
+}
+
+/* stark.py:59-79: D = C / Z with Z = (X^s - 1) / (X - r), as D = C (X - r) / (X^s - 1).  c: n coefficients with deg C < n - 1
+ * (so C (X - r) still has n coefficients); out: n coefficients of D (zero above its degree).  The division by the sparse
+ * X^s - 1 runs top down: q_i = a_{i+s} + q_{i+s}; the remainder a_i + q_i (i < s) must vanish (stark.py:76 asserts it).
+ * Returns 0, or -1 when the remainder is not zero (the witness is not a valid trace) or the shape is wrong. */
+int or_stark_d(const uint8_t* c, uint64_t n, uint64_t s, const uint8_t r_wire[32], uint8_t* out) {
+  if (s == 0 || s > n) return -1;
+  fe r = fe_from_wire(r_wire);
+  fe* a = (fe*)malloc(sizeof(fe) * (n + 1));
+  fe* q = (fe*)calloc(n, sizeof(fe));
+  fe prev = fe_u64(0);
+  for (uint64_t i = 0; i < n; ++i) { /* a = C X - r C */
+    fe ci = fe_from_wire(c + 32 * i), rc = fe_mul(&r, &ci);
+    a[i] = fe_sub(&prev, &rc);
+    prev = ci;
+  }
+  a[n] = prev;
+  int rc = fe_is_zero(&a[n]) ? 0 : -1;
+  for (uint64_t i = n - s; rc == 0 && i-- > 0;) {
+    q[i] = a[i + s];
+    if (i + s < n) q[i] = fe_add(&q[i], &q[i + s]);
+  }
+  for (uint64_t i = 0; rc == 0 && i < s; ++i) {
+    fe t = fe_add(&a[i], &q[i]);
+    if (!fe_is_zero(&t)) rc = -1;
+  }
+  if (rc == 0)
+    for (uint64_t i = 0; i < n; ++i) fe_to_wire(&q[i], out + 32 * i);
+  free(q);
+  free(a);
+  return rc;
+}
+
+/* polynomial.py:121-143 for a monic linear divisor X - r (synthetic division): a has n coefficients, out gets the n - 1
+ * coefficients of the quotient; the remainder is dropped, as stark.py:98-101 drops p_divmod's. */
+void or_div_linear(const uint8_t* a, uint64_t n, const uint8_t r_wire[32], uint8_t* out) {
+  fe r = fe_from_wire(r_wire), carry = fe_u64(0);
+  for (uint64_t i = n; i-- > 1;) {
+    fe ai = fe_from_wire(a + 32 * i), t = fe_mul(&carry, &r);
+    carry = fe_add(&ai, &t);
+    fe_to_wire(&carry, out + 32 * (i - 1));
+  }
+}
+
+/* out_i = sum_e scal[e] * cols[e][i] over k columns of n elements (stark.py:128-177: the linear combination l). */
+void or_lincomb(const uint8_t* cols, uint32_t k, uint64_t n, const uint8_t* scal, uint8_t* out) {
+  fe* s = (fe*)malloc(sizeof(fe) * k);
+  for (uint32_t e = 0; e < k; ++e) s[e] = fe_from_wire(scal + 32 * e);
+  for (uint64_t i = 0; i < n; ++i) {
+    fe y = fe_u64(0);
+    for (uint32_t e = 0; e < k; ++e) {
+      fe x = fe_from_wire(cols + 32 * (e * n + i)), t = fe_mul(&s[e], &x);
+      y = fe_add(&y, &t);
+    }
+    fe_to_wire(&y, out + 32 * i);
+  }
+  free(s);
+}
+
+/* merkle_tree.py:94-119 (merkelize_polynomial_evaluations): leaf x = cols[0][x] || ... || cols[k-1][x], the leaves
+ * permuted as merkle_tree.py:11-23 does and kept raw at the leaf level.  nodes: n x 32 B, nodes[0] = zeros, nodes[1] =
+ * root, nodes[i] = BLAKE2s(leaf pair or child pair); the leaf level itself is not written (the caller has the columns). */
+void or_merkelize_columns(const uint8_t* cols, uint32_t k, uint64_t n, uint8_t* nodes) {
+  uint64_t q = n / 4;
+  uint8_t* msg = (uint8_t*)malloc(64 * (size_t)k);
+  memset(nodes, 0, 32);
+  for (uint64_t i = n / 2; i < n; ++i)
+    for (int h = 0; h < 2; ++h) {
+      uint64_t pj = 2 * i + h - n, x = (pj & 3) * q + (pj >> 2); /* permuted leaf -> natural position */
+      for (uint32_t e = 0; e < k; ++e) memcpy(msg + 32 * ((size_t)h * k + e), cols + 32 * (e * n + x), 32);
+      if (h) or_blake2s(msg, 64 * (uint64_t)k, nodes + 32 * i);
+    }
+  for (uint64_t i = n / 2; i-- > 1;) or_blake2s(nodes + 64 * i, 64, nodes + 32 * i);
+  free(msg);
+}

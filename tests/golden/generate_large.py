@@ -10,6 +10,8 @@ reference cannot reach (BASELINE configs[3]).
     python3 tests/golden/generate_large.py --fri      # writes tests/golden/fri_large.json (about 3 min, 3 GB): below
     python3 tests/golden/generate_large.py --merkle   # writes tests/golden/merkle_large.json (about 1 min, 2 GB)
     python3 tests/golden/generate_large.py --stark [12 14 16]  # writes / extends tests/golden/stark_large.json: see stark_main
+    python3 tests/golden/generate_large.py --fast [-j N]  # the O(n log n) STARK oracle: stark_large.json (2^18, 2^20),
+                                                         # stark_units.json, stark_variants.json (about 5 min on 8 cores): fast_main
 
 2^17 is the domain of config 3's commit, whose default plan (9, 8) the reference-generated fixtures reach only through the
 sparse first pass (a dense vector of that length: here).  2^19 is the domain of config 5's proofs (plan (9, 10)), 2^21 the first three-pass plan, 2^23 the domain of the metric's
@@ -27,8 +29,10 @@ round and its Lagrange fold), its length, the first round's root2 and the final 
 reach these sizes (2^14 steps take it 20 s, 2^20 would take hours); the C oracle is pinned to it on the 2^14-step MiMC commit and
 seven smaller ones (tests/golden/fri.json, tests/test_coracle.py)."""
 import hashlib
+import itertools
 import json
 import os
+import random
 import struct
 import sys
 import time
@@ -120,6 +124,160 @@ def stark_main():
                                     "pinned to the reference by stark.json)", "cases": cases}, fh, indent=1)
 
 
+# ---- --fast: oracle/fastoracle.py:mk_stark_proof_fast (exact, O(n log n); tests/test_stark_oracle.py pins it to the reference's
+# proofs and to pyoracle.mk_stark_proof) -----------------------------------------------------------------------------------------
+FAST_GENERATOR = "oracle/fastoracle.py:mk_stark_proof_fast"
+FAST_LOGSTEPS = (18, 20)          # stark_large.json: config 5's unit 0 beyond 2^16 steps (2^20 is bench.py's stark_prove leg)
+UNITS = (1, 63, 64, 127, 128, 255, 256, 511)  # config 5 units on the shard boundaries of 2, 4 and 8 GPUs (512 units)
+MIMC_SP = [{(1, 0): 1}, {(1, 0): 1, (0, 3): 1}]
+VARIANT_SEED = 0x57A2
+
+
+def _seeded(seed, i):
+    return int.from_bytes(hashlib.blake2s(struct.pack("<QQ", seed, i)).digest(), "big") % P
+
+
+def variant_inputs(seed, width, unit):
+    """Inputs of unit `unit` of a stark_variants.json case (distinct for every unit of a batch)."""
+    return [_seeded(seed, unit * width + j) for j in range(width)]
+
+
+def _variant_polys(width, rng):
+    """Random step polynomials of one width: 1-4 terms per dimension, coefficients among 1, 2, p - 1 and random ones; a constant
+    term, a term touching every variable (degree = width), every dimension of degree >= 1 somewhere."""
+    sp = []
+    for j in range(width):
+        terms = {}
+        ex = [0] * width
+        ex[(j + 1) % width] = rng.choice([1, 2, 3])  # dimension j moves with the next one
+        terms[tuple(ex)] = rng.choice([1, 2, P - 1, rng.randrange(1, P)])
+        for _ in range(rng.randint(0, 2)):
+            ex = [0] * width
+            for _ in range(rng.randint(1, 3)):
+                ex[rng.randrange(width)] += 1
+            terms[tuple(ex)] = rng.choice([1, 2, P - 1, rng.randrange(1, P)])
+        sp.append(terms)
+    sp[0][(0,) * width] = P - 1                      # a constant term
+    sp[-1][(1,) * width] = rng.choice([1, P - 1])    # a term touching every variable
+    return sp
+
+
+def variant_cases():
+    """The shapes of stark_variants.json.  rows = steps * ext / 4 * batch decides which kernel instance stark.hip launches
+    (STARK_WIDE_THREADS, SHK_STARK_SPLIT_LOG there; tests/test_gpu_parity.py derives the regimes from the source and asserts that
+    every cell has a case): for every width a narrow (rows <= 2^16), a middle (2^17 < rows < 2^19) and a WIDE (rows >= 2^19) batch;
+    the band 2^16 < rows <= 2^17 for widths 1, 2 and 5; width 2 on both sides of each threshold."""
+    rng = random.Random(VARIANT_SEED)
+    cases = []
+
+    def add(name, width, sp, steps, ext, batch):
+        cases.append({"name": name, "width": width, "steps": steps, "ext": ext, "batch": batch, "seed": VARIANT_SEED + len(cases),
+                      "step_polys": [[[list(k), v] for k, v in sorted(d.items())] for d in sp]})
+
+    polys = {w: _variant_polys(w, rng) for w in range(1, 10)}
+    exts = {1: (4, 8, 8), 2: (8, 4, 16), 3: (16, 8, 8), 4: (4, 16, 32), 5: (8, 8, 16), 6: (16, 8, 32), 7: (8, 16, 16),
+            8: (16, 8, 32), 9: (16, 32, 16)}
+    for w in range(1, 10):
+        sp = polys[w]
+        deg = max(sum(k) for d in sp for k in d)
+        en, em, ew = exts[w]
+        assert all(deg * (s - 1) + 1 < s * e for s, e in ((1 << 9, en), (1 << 11, em), (1 << 12, ew))), (w, deg)
+        add("w%d_narrow" % w, w, sp, 1 << 9, en, 3)
+        r = (1 << 11) * em // 4
+        add("w%d_middle" % w, w, sp, 1 << 11, em, (1 << 17) // r + 5 + w)
+        r = (1 << 12) * ew // 4
+        add("w%d_wide" % w, w, sp, 1 << 12, ew, (1 << 19) // r + 1)
+    # the lincomb band 2^16 < rows <= 2^17 (quotients narrow, lincomb middle) for the W = 1, W = 2 and generic instances
+    for w in (1, 2, 5):
+        add("w%d_band" % w, w, polys[w], 1 << 10, 8, 45)
+    # width 2 on both sides of each threshold: one proof is 2^13 rows
+    for tag, b in (("rows_2^16", 8), ("rows_2^17", 16), ("rows_2^17+1p", 17), ("rows_2^19-1p", 63), ("rows_2^19", 64)):
+        add("w2_" + tag, 2, polys[2], 1 << 12, 8, b)
+    # the library's 256-term limit: width 9, the first 256 monomials of degree <= 4 in turn, round robin over the dimensions
+    mons = sorted({tuple(sum(1 for v in pick if v == i) for i in range(9)) for pick in itertools.combinations_with_replacement(
+        range(10), 4)})  # variable 9 stands for "none": degrees 0 ... 4
+    big = [{} for _ in range(9)]
+    for t, ex in enumerate(mons[:256]):
+        big[t % 9][ex] = rng.choice([1, P - 1, rng.randrange(1, P)])
+    add("w9_256_terms", 9, big, 1 << 8, 16, 5)
+    return cases
+
+
+def _prove_one(job):
+    """Worker: one proof by the fast oracle -> (sha256 hex, flat bytes length, m_root, l_root, outputs, seconds)."""
+    from oracle import fastoracle as fo
+    from oracle import pyoracle as po
+    inputs, steps, ext, sp = job
+    t0 = time.time()
+    w = po.get_computational_trace(inputs, steps, sp)
+    proof = fo.mk_stark_proof_fast(w, inputs, sp, steps, ext)
+    flat = po.stark_flat(proof)
+    return (hashlib.sha256(flat).hexdigest(), len(flat), proof[0].hex(), proof[1].hex(), ["%064x" % col[-1] for col in w],
+            time.time() - t0)
+
+
+def _dump(path, generator, cases):
+    with open(path, "w") as fh:
+        json.dump({"generator": generator, "cases": cases}, fh, indent=1)
+
+
+def fast_main():
+    """--fast [-j N]: the STARK fixtures the O(n log n) oracle writes.  It first reproduces the committed 2^12 / 2^14 / 2^16 cases of
+    stark_large.json (written by the quadratic pyoracle prover) and stops unless every byte agrees; then it proves, in N worker
+    processes, config 5's unit 0 at 2^18 and 2^20 steps (stark_large.json), units UNITS at 2^16 steps (stark_units.json) and the kernel
+    variant matrix of variant_cases() (stark_variants.json).  Apart from oracle_seconds a re-run rewrites all three files byte for byte."""
+    from multiprocessing import Pool
+    from oracle import fastoracle as fo
+    from oracle import pyoracle as po
+    nproc = int(sys.argv[sys.argv.index("-j") + 1]) if "-j" in sys.argv else (os.cpu_count() or 1)
+    large_path = os.path.join(HERE, "stark_large.json")
+    with open(large_path) as fh:
+        large = json.load(fh)
+    old = [c for c in large["cases"] if c["logsteps"] not in FAST_LOGSTEPS]
+    for c in old:
+        w = po.get_computational_trace(c["inputs"], c["steps"], MIMC_SP)
+        flat = po.stark_flat(fo.mk_stark_proof_fast(w, c["inputs"], MIMC_SP, c["steps"], c["ext"]))
+        assert hashlib.sha256(flat).hexdigest() == c["proof_sha256"] and len(flat) == c["proof_bytes"], c["logsteps"]
+        print("reproduced stark_large.json 2^%d" % c["logsteps"], flush=True)
+        c.setdefault("generator", "oracle/pyoracle.py:mk_stark_proof")
+    variants = variant_cases()
+    jobs = [([42, 3], 1 << ls, 8, MIMC_SP) for ls in FAST_LOGSTEPS]
+    jobs += [([42, 3 + j], 1 << 16, 8, MIMC_SP) for j in UNITS]
+    for v in variants:
+        sp = [{tuple(k): c for k, c in d} for d in v["step_polys"]]
+        jobs += [(variant_inputs(v["seed"], v["width"], u), v["steps"], v["ext"], sp) for u in range(v["batch"])]
+    with Pool(nproc) as pool:
+        res = pool.map(_prove_one, jobs, chunksize=1)
+    it = iter(res)
+    new = []
+    for ls in FAST_LOGSTEPS:
+        sha, nb, m, l, outs, sec = next(it)
+        new.append({"logsteps": ls, "steps": 1 << ls, "ext": 8, "width": 2, "inputs": [42, 3], "unit": 0,
+                    "step_polys": [[[list(k), v] for k, v in sorted(d.items())] for d in MIMC_SP], "samples": 80, "outputs": outs,
+                    "m_root": m, "l_root": l, "proof_bytes": nb, "proof_sha256": sha, "generator": FAST_GENERATOR,
+                    "oracle_seconds": round(sec, 1)})
+    large["cases"] = sorted(old + new, key=lambda c: c["logsteps"])
+    units = []
+    for j in UNITS:
+        sha, nb, m, l, outs, sec = next(it)
+        units.append({"unit": j, "steps": 1 << 16, "ext": 8, "width": 2, "inputs": [42, 3 + j], "samples": 80, "outputs": outs,
+                      "m_root": m, "l_root": l, "proof_bytes": nb, "proof_sha256": sha, "generator": FAST_GENERATOR,
+                      "oracle_seconds": round(sec, 1)})
+    for v in variants:
+        got = [next(it) for _ in range(v["batch"])]
+        v["proof_bytes"] = got[0][1]
+        v["unit_sha256"] = [g[0] for g in got]
+        v["generator"] = FAST_GENERATOR
+        v["oracle_seconds"] = round(sum(g[5] for g in got), 1)
+    _dump(large_path, "tests/golden/generate_large.py --stark (oracle/pyoracle.py:mk_stark_proof, the coefficient-form prover "
+                      "pinned to the reference by stark.json) and --fast (oracle/fastoracle.py:mk_stark_proof_fast, pinned to it)", large["cases"])
+    _dump(os.path.join(HERE, "stark_units.json"), "tests/golden/generate_large.py --fast (%s): config 5 units (inputs [42, 3 + unit], "
+          "step polynomials [X1, X1 + X2^3]) at 2^16 steps" % FAST_GENERATOR, units)
+    _dump(os.path.join(HERE, "stark_variants.json"), "tests/golden/generate_large.py --fast (%s): generate_large.variant_cases(); "
+          "unit u of a case has inputs generate_large.variant_inputs(seed, width, u) and the witness "
+          "pyoracle.get_computational_trace(inputs, steps, step_polys)" % FAST_GENERATOR, variants)
+
+
 def merkle_main():
     """--merkle: the Merkle commitment bench.py times (2^24 leaves x_i = BLAKE2s(seed_le64 || i_le64) mod p, seed 7, and the 2^20-leaf
     one of its --quick mode) hashed by oracle/oracle.c:or_merkelize (merkle_tree.py:36-56 with permute4): the root, three interior
@@ -155,6 +313,8 @@ def main():
         return merkle_main()
     if "--fri" in sys.argv[1:]:
         return fri_main()
+    if "--fast" in sys.argv[1:]:
+        return fast_main()
     if "--stark" in sys.argv[1:]:
         return stark_main()
     out = os.path.join(HERE, "ntt_large.json")

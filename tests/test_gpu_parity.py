@@ -893,7 +893,8 @@ def _stark_large_cases():
 def test_stark_proofs_at_size_vs_coefficient_form_oracle_fixture(sa, c):
     """Whole STARK proofs of config 5's unit 0 at 2^12, 2^14 and 2^16 steps (config 5's own size) byte for byte against the proofs the
     COEFFICIENT-FORM prover of oracle/pyoracle.py wrote (the reference's construction, quadratic: 9 min for 2^14 steps, hours for 2^16;
-    tests/golden/stark_large.json, generate_large.py --stark) -- through the host-buffer entry point, and through the device-resident
+    tests/golden/stark_large.json, generate_large.py --stark), and at 2^18 and 2^20 steps against its O(n log n) restatement
+    oracle/fastoracle.py (generate_large.py --fast) -- through the host-buffer entry point, and through the device-resident
     batched one that bench.py's config 5 times (unit 0 inside a batch of 4)."""
     import ctypes
     from starks_amd import batch, stark
@@ -1016,6 +1017,77 @@ def test_stark_wide_state_medium_trace(sa, oracle):
     assert po.verify_stark_proof(pr, [c[-1] for c in w9], inputs9, sp9, steps9, ext)
 
 
+def _variant_cases():
+    try:
+        return load_golden("stark_variants.json")["cases"]
+    except Exception:
+        return []
+
+
+@pytest.mark.parametrize("c", _variant_cases(), ids=lambda c: c["name"])
+def test_stark_kernel_variant_matrix(sa, c):
+    """One batch of tests/golden/stark_variants.json (generate_large.py --fast: the O(n log n) coefficient-form oracle): every unit
+    of the batch, proved in ONE launch through the host-buffer entry point and through the device-resident one, equals its fixture
+    hash.  Together the cases reach every kernel instance stark.hip launches -- the quotient kernel for W = 1..9 and the lincomb
+    kernel for W = 1, 2 and generic, narrow / middle / WIDE -- and width 2 on both sides of each threshold (tests/stark_variants.py
+    reads the thresholds from the kernel source).  Each unit has its own inputs, so a unit-offset bug shows as wrong bytes in a unit."""
+    import ctypes
+    import stark_variants as sv
+    from starks_amd import stark
+    from starks_amd.multivariate_polynomial import multivariates_over
+    (q, w), (lc, lw) = sv.regimes(c)
+    print("%s: rows %d -> quotients %s<W=%d>, lincomb %s<W=%s>" % (c["name"], sv.rows(c), q, w, lc, lw or "generic"))
+    steps, ext, width, nb = c["steps"], c["ext"], c["width"], c["batch"]
+    sp = sv.step_polys(c)
+    mv = multivariates_over(sa.F, width).factory
+    polys = [mv(d) for d in sp]
+    ins = [sv.unit_inputs(c, u) for u in range(nb)]
+    wit = b"".join(b"".join(wire(col) for col in sv.trace(i, steps, sp)) for i in ins)
+    inp = b"".join(wire(i) for i in ins)
+    plen = c["proof_bytes"]
+    coefs, exps, counts, degree = stark.pack_step_polys(polys, width)
+    assert stark.proof_len(steps, ext, width, degree) == plen
+
+    def check(flat, path):
+        assert len(flat) == plen * nb
+        bad = [u for u in range(nb) if hashlib.sha256(flat[u * plen:(u + 1) * plen]).hexdigest() != c["unit_sha256"][u]]
+        assert not bad, "%s path, %s: units %s of %d differ from the oracle" % (path, c["name"], bad[:16], nb)
+
+    check(stark.prove_flat(wit, inp, steps, ext, width, polys, batch=nb), "host")
+    L, ctx = sa.lib.lib(), sa.lib.ctx()
+    bufs = [ctypes.c_void_p() for _ in range(3)]
+    try:
+        for ptr, nbytes in zip(bufs, (len(wit), len(inp), plen * nb)):
+            sa.lib.check(L.sh_dev_alloc(ctx, nbytes, ctypes.byref(ptr)), "alloc")
+        dw, di, dp = bufs
+        sa.lib.check(L.sh_dev_from_wire(ctx, wit, dw, len(wit) // 32), "w")
+        sa.lib.check(L.sh_dev_from_wire(ctx, inp, di, len(inp) // 32), "i")
+        sa.lib.check(L.sh_dev_stark_prove(ctx, dw, di, steps, ext, width, coefs, exps, counts, 80, nb, dp), "prove")
+        out = ctypes.create_string_buffer(plen * nb)
+        sa.lib.check(L.sh_dev_download(ctx, dp, out, plen * nb), "dl")
+        assert L.sh_stark_status(ctx) == 0
+    finally:
+        for ptr in bufs:
+            if ptr.value:
+                sa.lib.check(L.sh_dev_free(ctx, ptr), "free")
+    check(out.raw, "device")
+
+
+def test_stark_kernel_variant_matrix_covers_every_cell(sa):
+    """The variant matrix has a case in every kernel cell, with the thresholds read from stark.hip (also checked on the CPU,
+    tests/test_stark_oracle.py); printed per cell."""
+    import stark_variants as sv
+    cases = _variant_cases()
+    th = sv.thresholds()
+    by_cell = {}
+    for c in cases:
+        for cell in sv.cells_of(c, th):
+            by_cell.setdefault(cell, []).append(c["name"])
+    for cell in sorted(sv.required_cells(th), key=str):
+        print("covered" if cell in by_cell else "MISSING", cell, by_cell.get(cell, []))
+    assert sv.required_cells(th) <= set(by_cell)
+
+
 def test_full_size_merkle_2_24_branches_verify(sa):
     """A 2^24-leaf tree (1 GiB of nodes) built on the device: random branches, fetched node by node, verify against the
     root with the host verifier, and their leaves are the seeded values (merkle_tree.py:59-86)."""
@@ -1115,9 +1187,16 @@ def test_config5_all_512_units_at_size(sa, oracle):
     from starks_amd import batch, stark
     from starks_amd.multivariate_polynomial import generate_Xi_s
     steps, ext, total = 1 << 16, 8, 512
-    sample = {0, 31, 32, 257, 511}
+    fixture = {c["unit"]: c for c in load_golden("stark_units.json")["cases"]}
+    assert set(fixture) == {1, 63, 64, 127, 128, 255, 256, 511}  # the shard boundaries of 2, 4 and 8 GPUs
+    sample = {0, 31, 32, 257, 511} | set(fixture)
     digs, kept = batch.prove_stark_units_device(0, total, steps, ext, chunk=32, keep=sample)
     assert len(digs) == total and len(set(digs)) == total and set(kept) == sample
+    # the kept units against the O(n log n) coefficient-form oracle (tests/golden/stark_units.json, generate_large.py --fast)
+    for j, c in sorted(fixture.items()):
+        assert (c["steps"], c["ext"], c["inputs"]) == (steps, ext, batch.mimc_stark_unit(j, 2)[1]), j
+        assert len(kept[j]) == c["proof_bytes"] and kept[j][:32].hex() == c["m_root"] and kept[j][32:64].hex() == c["l_root"], j
+        assert hashlib.sha256(kept[j]).hexdigest() == c["proof_sha256"], j
     for j in sorted(sample):
         (jj, alone), = batch.prove_stark_batch([j], steps, ext, chunk=1)
         assert jj == j and alone == kept[j], j
