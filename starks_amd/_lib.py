@@ -98,6 +98,10 @@ def lib():
         "sh_ctx_set_plan_budget": (i32, [c_p, u64]),
         "sh_ctx_stats": (i32, [c_p, ctypes.POINTER(u64)]),
         "sh_dev_fill_mimc_units": (i32, [c_p, c_p, c_p, u64, u32, u32, u32]),
+        "sh_dev_stark_verify": (i32, [c_p, c_p, c_p, c_p, u64, u64, u32, u32, u8p, u8p, ctypes.POINTER(u32), u32, u32, c_p]),
+        "sh_dev_fri_verify": (i32, [c_p, c_p, c_p, u64, u8p, u64, u32, u32, u32, c_p]),
+        "sh_stark_verify_batch": (i32, [c_p, u8p, u64, u8p, u8p, u64, u32, u32, u8p, u8p, ctypes.POINTER(u32), u32, u32, c_p]),
+        "sh_fri_verify_batch": (i32, [c_p, u8p, u64, u8p, u64, u8p, u64, u32, u32, u32, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares

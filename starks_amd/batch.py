@@ -162,6 +162,7 @@ class StarkUnitProver(object):
         if self.plen == 0:
             raise NotImplementedError("unsupported shape (steps=%d, ext=%d)" % (steps, ext))
         self.dw, self.di, self.dp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self.ds = None  # verify()'s statuses, allocated on first use
         for ptr, nbytes in ((self.dw, 64 * steps * chunk), (self.di, 64 * chunk), (self.dp, self.plen * chunk)):
             _lib.check(self.L.sh_dev_alloc(self.ctx, nbytes, ctypes.byref(ptr)), "sh_dev_alloc")
 
@@ -194,11 +195,29 @@ class StarkUnitProver(object):
         raw = out.raw
         return [raw[i * self.plen:(i + 1) * self.plen] for i in range(k)]
 
+    def verify(self, k):
+        """Verifies the k proofs prove() left on the device, on the device (sh_dev_stark_verify), in stream order behind the prover:
+        no synchronisation between the two.  The boundary values are read from the device witness through io_stride = steps:
+        witness[dim][0] = the inputs generate() wrote, witness[dim][-1] = the outputs (stark.py:370).  -> [int] statuses
+        (0 = accepted, -9 = rejected), each what sh_stark_verify returns for that proof."""
+        import ctypes
+        if not 1 <= k <= self.chunk:
+            raise ValueError("k must be 1 .. chunk (%d): the device buffers hold chunk proofs" % self.chunk)
+        if self.ds is None:
+            self.ds = ctypes.c_void_p()
+            self._lib.check(self.L.sh_dev_alloc(self.ctx, 4 * self.chunk, ctypes.byref(self.ds)), "sh_dev_alloc")
+        last = ctypes.c_void_p(self.dw.value + 32 * (self.steps - 1))
+        self._lib.check(self.L.sh_dev_stark_verify(self.ctx, self.dp, self.dw, last, self.steps, self.steps, self.ext, 2, self.coefs,
+                                                   self.exps, self.counts, 80, k, self.ds), "sh_dev_stark_verify")
+        out = (ctypes.c_int32 * k)()
+        self._lib.check(self.L.sh_dev_download(self.ctx, self.ds, out, 4 * k), "sh_dev_download")
+        return list(out)
+
     def close(self):
-        for ptr in (self.dw, self.di, self.dp):
+        for ptr in (self.dw, self.di, self.dp, self.ds):
             if ptr:
                 self.L.sh_dev_free(self.ctx, ptr)
-        self.dw = self.di = self.dp = None
+        self.dw = self.di = self.dp = self.ds = None
 
 
 def digest(proof_bytes):

@@ -410,43 +410,7 @@ __global__ void __launch_bounds__(4 * QUADS) merkle_top_kernel(uint32_t* nodes, 
 }
 
 // ---- query sampling + branch gather --------------------------------------------------------------------
-// get_pseudorandom_indices(root, modulus, samples, exclude_multiples_of) (utils.py:60-90): one QUAD of lanes per proof.
-// data = root, then data += blake(data[-32:]) (utils.py:74-75): a serial chain, so each 32-byte block is hashed
-// with the low-latency quad-lane BLAKE2s; after block k lane q holds words q and 4+q = samples 8k+q and 8k+4+q.
-__device__ __forceinline__ void sample_indices_quad(uint32_t* slots, const uint32_t* root, bool live, uint32_t modulus, uint32_t samples,
-                                                    uint32_t exclude, uint32_t* ys) {
-  const uint32_t tid = threadIdx.x, quad = tid >> 2, q = tid & 3;
-  b2q_addr ad;
-  b2q_addr_init(ad, quad * 64, q);
-  uint32_t w_lo = 0, w_hi = 0;
-  if (live) {
-    w_lo = root[q];
-    w_hi = root[4 + q];
-  }
-  uint32_t* slot = slots + quad * 16;
-  slot[8 + q] = 0;   // a 32-byte message: words 8..15 are zero padding
-  slot[12 + q] = 0;
-  const uint32_t real = exclude ? (uint32_t)(((uint64_t)modulus * (exclude - 1)) / exclude) : modulus;
-  const uint32_t blocks = (samples + 7) / 8;
-  for (uint32_t k = 0; k < blocks; ++k) {
-    if (live) {
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const uint32_t j = 8 * k + 4 * half + q;
-        if (j < samples) {
-          const uint32_t x = __builtin_bswap32(half ? w_hi : w_lo) % real;  // int.from_bytes(data[4j:4j+4], 'big') % modulus
-          ys[j] = exclude ? x + 1 + x / (exclude - 1) : x;
-        }
-      }
-    }
-    if (k + 1 == blocks) break;
-    slot[q] = w_lo;
-    slot[4 + q] = w_hi;
-    __syncthreads();
-    b2q_compress(ad, slots, q, 32, w_lo, w_hi);
-    __syncthreads();
-  }
-}
+// sample_indices_quad (blake2s.cuh): get_pseudorandom_indices with one quad of lanes per index set.
 __global__ void __launch_bounds__(64) sample_indices_kernel(const uint32_t* nodes, uint64_t tree_words, uint32_t modulus,
                                                             uint32_t batch, uint32_t samples, uint32_t exclude,
                                                             uint32_t* ys_out) {

@@ -174,6 +174,21 @@ def verify_flat(flat, merkle_root, n, root_of_unity, maxdeg_plus_1, exclude_mult
     return True
 
 
+def verify_flat_batch(flats, merkle_roots, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0, batch=1, samples=40):
+    """`batch` flat proofs of one shape verified on the GPU in one call (sh_fri_verify_batch): flats = the proofs back to back,
+    merkle_roots = their batch 32-byte committed roots.  -> [bool] per proof, each the decision verify_flat takes on that proof
+    alone.  Shape errors raise as verify_flat raises them."""
+    flats = bytes(flats)
+    if batch < 1 or len(flats) % batch:
+        raise ValueError("flats must hold batch proofs of equal length")
+    status = (ctypes.c_int32 * batch)()
+    rc = _lib.lib().sh_fri_verify_batch(_lib.ctx(), flats, len(flats) // batch, bytes(merkle_roots), n,
+                                        int(root_of_unity).to_bytes(32, "big"), maxdeg_plus_1, exclude_multiples_of, samples, batch,
+                                        status)
+    _lib.check(rc, "sh_fri_verify_batch")  # a shape error, or a proof length that is not the shape's
+    return [s == 0 for s in status]
+
+
 class SmoothSubgroupFRI(object):
     """fri.py:176-366 (class name and method signatures of the reference's commented-out driver)."""
 

@@ -128,6 +128,21 @@ def verify_flat(flat, input_bytes, output_bytes, steps, ext, width, step_polys, 
     return True
 
 
+def verify_flat_batch(flats, input_bytes, output_bytes, steps, ext, width, step_polys, batch, samples=SPOT_CHECKS):
+    """`batch` flat proofs of one shape verified on the GPU in one call (sh_stark_verify_batch): flats = the proofs back to back,
+    input_bytes / output_bytes = [batch][width] wire-form boundary inputs and witness[dim][-1].  -> [bool] per proof, each the
+    decision verify_flat takes on that proof alone.  Shape errors raise as verify_flat raises them."""
+    coefs, exps, counts, _ = pack_step_polys(step_polys, width)
+    flats = bytes(flats)
+    if batch < 1 or len(flats) % batch:
+        raise ValueError("flats must hold batch proofs of equal length")
+    status = (ctypes.c_int32 * batch)()
+    rc = _lib.lib().sh_stark_verify_batch(_lib.ctx(), flats, len(flats) // batch, bytes(input_bytes), bytes(output_bytes), steps, ext,
+                                          width, coefs, exps, counts, samples, batch, status)
+    _lib.check(rc, "sh_stark_verify_batch")  # a shape error, or a proof length that is not the shape's
+    return [s == 0 for s in status]
+
+
 class STARK(object):
     """Generates and verifies STARKs (stark.py:179-402); same constructor arguments."""
 
