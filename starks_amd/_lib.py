@@ -102,6 +102,8 @@ def lib():
         "sh_dev_fri_verify": (i32, [c_p, c_p, c_p, u64, u8p, u64, u32, u32, u32, c_p]),
         "sh_stark_verify_batch": (i32, [c_p, u8p, u64, u8p, u8p, u64, u32, u32, u8p, u8p, ctypes.POINTER(u32), u32, u32, c_p]),
         "sh_fri_verify_batch": (i32, [c_p, u8p, u64, u8p, u64, u8p, u64, u32, u32, u32, c_p]),
+        "sh_dev_stark_witness": (i32, [c_p, c_p, u64, u32, u8p, u8p, c_p, u32, c_p]),
+        "sh_stark_witness": (i32, [c_p, u8p, u64, u32, u8p, u8p, c_p, u32, c_p, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares

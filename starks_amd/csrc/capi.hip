@@ -13,7 +13,10 @@
 #include "internal.hpp"
 #include "knobs.hpp"
 #include "verify_items.cuh"
+#include "witness_items.cuh"
 
+// witness.hip
+hipError_t shk_stark_witness_slice(const WitnessArgs& a, uint32_t width, hipStream_t st);
 // verify_dev.hip
 hipError_t shk_verify_batch(const VbPlan& p, const uint8_t* proofs, uint32_t batch, const uint8_t* roots, const fp* inputs,
                             const fp* outputs, uint64_t io_stride, const fp* coef, const uint8_t* exps, uint32_t row,
@@ -1566,6 +1569,76 @@ int sh_stark_prove(sh_ctx* c, const uint8_t* witness, const uint8_t* inputs, uin
   SH_TRY(run_stark(c, w, in, steps, ext, width, samples, batch, reinterpret_cast<uint8_t*>(dp)));
   SH_TRY(d2h(c, proof, dp, (size_t)stride * batch));
   return sh_stark_status(c);
+}
+
+// ---- AIR.generate_witness (air.py:32-52, 121-123) on the device: witness.hip, launched in slices of steps -------------------------
+static int witness_check(const void* in, const void* out, uint64_t steps, uint32_t width, const uint8_t* coefs, const uint8_t* exps,
+                         const uint32_t* counts, uint32_t batch) {
+  if (!in || !out || !coefs || !exps || !counts || steps == 0 || batch == 0 || width == 0) return SH_ERR_INVALID;
+  if (width > SHK_STARK_MAX_WIDTH) return SH_ERR_UNSUPPORTED;
+  uint64_t total = 0;
+  for (uint32_t d = 0; d < width; ++d) total += counts[d];
+  if (total == 0) return SH_ERR_INVALID;
+  if (total > SHK_STARK_MAX_TERMS) return SH_ERR_UNSUPPORTED;
+  const uint64_t cols = (uint64_t)batch * width;
+  if (cols > 0xffffffffull || steps > (~0ull / 32) / cols) return SH_ERR_UNSUPPORTED;  // the witness's byte count must fit 64 bits
+  return SH_OK;
+}
+
+// d_wit [batch][width][steps] from d_in [batch][width]; the terms are the ones stark_terms just uploaded
+static int run_witness(sh_ctx* c, const fp* d_in, fp* d_wit, uint64_t steps, uint32_t width, const uint8_t* coefs, const uint8_t* exps,
+                       const uint32_t* counts, uint32_t batch) {
+  WiRow rows[SHK_STARK_MAX_TERMS];
+  uint32_t T = 0;
+  const fp one = fp_one();
+  for (uint32_t d = 0; d < width; ++d)
+    for (uint32_t i = 0; i < counts[d]; ++i, ++T) rows[T] = wi_pack_row(d, fp_eq_canon(h_from_wire(coefs + 32ull * T), one), exps + (size_t)T * width, width);
+  WitnessArgs a;
+  memset(&a, 0, sizeof a);
+  wi_plan(rows, T, width, (uint32_t)shk_knobs().witness_group, (uint64_t)shk_knobs().witness_slice, &a.plan);
+  const uint8_t* tb = reinterpret_cast<const uint8_t*>(c->terms_dev);
+  a.inputs = d_in;
+  a.wit = d_wit;
+  a.steps = steps;
+  a.batch = batch;
+  a.nterms = T;
+  a.coef = reinterpret_cast<const fp*>(tb + TermLayout::coef);
+  a.exps = tb + TermLayout::exps;
+  memcpy(a.begin, c->terms_begin, sizeof a.begin);
+  for (a.k0 = 0; a.k0 < steps; a.k0 = a.k1) {  // each dispatch resumes from the last row the previous one wrote
+    a.k1 = steps - a.k0 > a.plan.slice ? a.k0 + a.plan.slice : steps;
+    HIP_TRY(c, shk_stark_witness_slice(a, width, c->stream));
+  }
+  return SH_OK;
+}
+
+int sh_dev_stark_witness(sh_ctx* c, const void* d_inputs, uint64_t steps, uint32_t width, const uint8_t* term_coefs,
+                         const uint8_t* term_exps, const uint32_t* term_counts, uint32_t batch, void* d_witness) {
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(witness_check(d_inputs, d_witness, steps, width, term_coefs, term_exps, term_counts, batch));
+  const uintptr_t i0 = (uintptr_t)d_inputs, i1 = i0 + 32ull * batch * width, w0 = (uintptr_t)d_witness,
+                  w1 = w0 + 32ull * batch * width * steps;
+  if (i0 < w1 && w0 < i1) return SH_ERR_INVALID;  // the buffers overlap
+  SH_TRY(enter(c));
+  SH_TRY(stark_terms(c, width, term_coefs, term_exps, term_counts));
+  return run_witness(c, reinterpret_cast<const fp*>(d_inputs), reinterpret_cast<fp*>(d_witness), steps, width, term_coefs, term_exps,
+                     term_counts, batch);
+}
+
+int sh_stark_witness(sh_ctx* c, const uint8_t* inputs, uint64_t steps, uint32_t width, const uint8_t* term_coefs, const uint8_t* term_exps,
+                     const uint32_t* term_counts, uint32_t batch, uint8_t* witness, uint64_t witness_cap) {
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(witness_check(inputs, witness, steps, width, term_coefs, term_exps, term_counts, batch));
+  const uint64_t count = (uint64_t)batch * width * steps;
+  if (witness_cap / 32 < count) return SH_ERR_TOO_SMALL;
+  SH_TRY(enter(c));
+  SH_TRY(stark_terms(c, width, term_coefs, term_exps, term_counts));
+  fp* in = nullptr;
+  SH_TRY(upload_padded(c, inputs, 1, 1, batch * width, sh_ctx::WS_Y, &in));
+  void* w = nullptr;
+  SH_TRY(ws_get(c, sh_ctx::WS_ST_TRACE, (size_t)count * sizeof(fp), &w));
+  SH_TRY(run_witness(c, in, reinterpret_cast<fp*>(w), steps, width, term_coefs, term_exps, term_counts, batch));
+  return download_wire(c, reinterpret_cast<fp*>(w), witness, count);
 }
 
 }  // extern "C"

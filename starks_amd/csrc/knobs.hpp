@@ -16,6 +16,8 @@
 //   STARKHIP_PLAN_CACHE_MB=m       initial plan-cache budget of a context
 //   STARKHIP_NTT_NARROW_TILES=k    passes of at most k 1024-element tiles (and radix <= 2^10) run in the one-butterfly-per-thread form
 //                                  (ntt_narrow_pass_kernel; default 256 = the CUs of the chip; 0 = never)
+//   STARKHIP_WITNESS_GROUP=1|2|4|8|16  lanes per unit of the witness generator (witness.hip; default: chosen from the term table)
+//   STARKHIP_WITNESS_SLICE=k       steps per witness dispatch (default: about 2^13 sequential products per dispatch, at least 1)
 // All of them exist for the parity tests over alternate plans (tests/test_gpu_parity.py::test_alternate_ntt_plans_parity,
 // tools/stress_plans.py) and for A/B measurements; the defaults are the measured best.
 #pragma once
@@ -35,6 +37,8 @@ struct ShkKnobs {
   int radices[4] = {0, 0, 0, 0};
   int radix_sum = 0;
   long narrow_tiles = 256;   // 0: the narrow form is never used
+  int witness_group = 0;     // 0: not given
+  long witness_slice = 0;    // 0: not given
 };
 
 namespace shk_knobs_detail {
@@ -74,6 +78,14 @@ inline void parse(ShkKnobs* k) {
   if (const char* e = getenv("STARKHIP_NTT_NARROW_TILES")) {
     const long v = atol(e);
     k->narrow_tiles = v < 0 ? 0 : v;
+  }
+  if (const char* e = getenv("STARKHIP_WITNESS_GROUP")) {
+    const int v = atoi(e);
+    if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) k->witness_group = v;
+  }
+  if (const char* e = getenv("STARKHIP_WITNESS_SLICE")) {
+    const long v = atol(e);
+    if (v > 0) k->witness_slice = v;
   }
   if (const char* e = getenv("STARKHIP_NTT_RADICES")) {
     int r[4] = {0, 0, 0, 0}, cnt = 0, sum = 0;

@@ -143,6 +143,58 @@ def verify_flat_batch(flats, input_bytes, output_bytes, steps, ext, width, step_
     return [s == 0 for s in status]
 
 
+def witness_flat(input_bytes, steps, width, step_polys, batch=1):
+    """AIR.generate_witness / get_computational_trace (air.py:32-52, 121-123) on the GPU (sh_stark_witness): input_bytes [batch][width]
+    wire form (values may be >= p) -> the witness [batch][width][steps] in wire form, what prove_flat takes.  Any steps >= 1."""
+    if len(input_bytes) != 32 * batch * width:
+        raise ValueError("inputs must hold batch*width 32-byte elements (got %d bytes for batch=%d, width=%d)"
+                         % (len(input_bytes), batch, width))
+    coefs, exps, counts, _ = pack_step_polys(step_polys, width)
+    nbytes = 32 * batch * width * steps
+    out = ctypes.create_string_buffer(nbytes)
+    _lib.check(_lib.lib().sh_stark_witness(_lib.ctx(), bytes(input_bytes), steps, width, coefs, exps, counts, batch, out, nbytes),
+               "sh_stark_witness")
+    return out.raw
+
+
+def prove_inputs_flat(input_bytes, steps, ext, width, step_polys, batch=1, samples=SPOT_CHECKS):
+    """Proofs straight from the inputs: upload them, then sh_dev_stark_witness -> sh_dev_stark_prove -> sh_stark_status on device
+    buffers (the witness never leaves the device).  -> (batch flat proofs concatenated, outputs): outputs = witness[b][dim][-1] as
+    [batch][width] wire form, the values sh_stark_verify / verify_flat_batch take beside the inputs."""
+    if len(input_bytes) != 32 * batch * width:
+        raise ValueError("inputs must hold batch*width 32-byte elements (got %d bytes for batch=%d, width=%d)"
+                         % (len(input_bytes), batch, width))
+    coefs, exps, counts, degree = pack_step_polys(step_polys, width)
+    plen = proof_len(steps, ext, width, degree, samples)
+    if plen == 0:
+        raise NotImplementedError("starks_amd.STARK: unsupported shape (steps=%d, ext=%d, width=%d, degree=%d)"
+                                  % (steps, ext, width, degree))
+    L, ctx = _lib.lib(), _lib.ctx()
+    di, dw, dp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    try:
+        for ptr, nbytes in ((di, 32 * batch * width), (dw, 32 * batch * width * steps), (dp, plen * batch)):
+            _lib.check(L.sh_dev_alloc(ctx, nbytes, ctypes.byref(ptr)), "sh_dev_alloc")
+        _lib.check(L.sh_dev_from_wire(ctx, bytes(input_bytes), di, batch * width), "sh_dev_from_wire")
+        _lib.check(L.sh_dev_stark_witness(ctx, di, steps, width, coefs, exps, counts, batch, dw), "sh_dev_stark_witness")
+        _lib.check(L.sh_dev_stark_prove(ctx, dw, di, steps, ext, width, coefs, exps, counts, samples, batch, dp), "sh_dev_stark_prove")
+        rc = L.sh_stark_status(ctx)
+        if rc == -8:  # a generated witness is a valid trace by construction: this would be a library fault
+            raise AssertionError("constraint polynomial is not a multiple of Z: the generated witness is not a valid trace")
+        _lib.check(rc, "sh_stark_status")
+        proofs = ctypes.create_string_buffer(plen * batch)
+        _lib.check(L.sh_dev_download(ctx, dp, proofs, plen * batch), "sh_dev_download")
+        last = ctypes.create_string_buffer(32 * batch * width)  # witness[b][dim][steps - 1], canonical limb form
+        _lib.check(L.sh_dev_download_2d(ctx, ctypes.c_void_p(dw.value + 32 * (steps - 1)), 32 * steps, last, 32, batch * width),
+                   "sh_dev_download_2d")
+    finally:
+        for ptr in (di, dw, dp):
+            if ptr.value:
+                L.sh_dev_free(ctx, ptr)
+    raw = last.raw
+    outputs = b"".join(raw[i:i + 32][::-1] for i in range(0, len(raw), 32))  # limbs are little-endian: reversed = wire form
+    return proofs.raw, outputs
+
+
 class STARK(object):
     """Generates and verifies STARKs (stark.py:179-402); same constructor arguments."""
 
