@@ -10,9 +10,11 @@
 // Every function is total on [0, 2^256) inputs (double folds are handled), so unreduced inputs such as
 // field(b'\xff'*32) (modp.py:33-34) are safe.
 //
-// All functions are __host__ __device__: the same code builds the twiddle tables on the host and is
-// exercised on the CPU through the table builders; the device code is pinned by tests/test_gpu_parity.py
-// (test_rare_carry_branches, the NTT / FRI / STARK parity tests) against the oracle.
+// All functions are __host__ __device__: the same code builds the twiddle tables on the host and runs on the
+// device.  Each primitive is pinned against exact integers, rare carry and borrow branches and raw products
+// included, by tests/test_field_arith_host.py (the portable C paths) and tests/test_gpu_field_arith.py (the
+// device paths, with and without SHK_NO_ADD_ASM, with rare lanes placed on every lane of a wave), both through
+// tests/native/fp256_ops.hip; tests/test_gpu_parity.py checks the kernels built on them against the oracle.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

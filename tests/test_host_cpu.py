@@ -198,7 +198,8 @@ def test_generated_asm_includes_are_current(tmp_path):
 def test_pair_constant_product_on_the_host(tmp_path):
     """fp_mul2 (csrc/fp256.cuh: the product by a table constant kept as the pair (w, w 2^128 mod p), what every NTT
     butterfly uses) against fp_mul through the portable C paths of the same header: 400 k random and edge operands, canonical
-    and lazily reduced second images.  The device's inline-asm path is pinned by the GPU parity tests and lab/r01_r03/mul2_bench.hip."""
+    and lazily reduced second images.  Both products, and every other primitive of the header, are pinned against exact integers by
+    tests/test_field_arith_host.py (these host paths) and tests/test_gpu_field_arith.py (the device's inline-asm paths)."""
     import subprocess
     src = os.path.join(ROOT, "tests", "native", "mul2_host.cpp")
     exe = tmp_path / "mul2_host"
