@@ -104,6 +104,10 @@ def lib():
         "sh_fri_verify_batch": (i32, [c_p, u8p, u64, u8p, u64, u8p, u64, u32, u32, u32, c_p]),
         "sh_dev_stark_witness": (i32, [c_p, c_p, u64, u32, u8p, u8p, c_p, u32, c_p]),
         "sh_stark_witness": (i32, [c_p, u8p, u64, u32, u8p, u8p, c_p, u32, c_p, u64]),
+        "sh_dev_multi_inv": (i32, [c_p, c_p, c_p, u64]),
+        "sh_multi_inv": (i32, [c_p, u8p, u64, c_p]),
+        "sh_dev_multi_interp_4": (i32, [c_p, c_p, c_p, u64, c_p]),
+        "sh_multi_interp_4": (i32, [c_p, u8p, u8p, u64, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares

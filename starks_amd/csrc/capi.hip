@@ -116,6 +116,7 @@ struct sh_ctx {
     WS_WIRE = 0, WS_X, WS_Y, WS_NTT, WS_TREE_A, WS_TREE_B, WS_COL_A, WS_COL_B, WS_MISC, WS_PROOF,
     WS_ST_TRACE, WS_ST_P, WS_ST_D, WS_ST_B, WS_ST_Q, WS_ST_SMALL, WS_ST_MTREE,
     WS_VB, WS_VB_IO,  // batch verifiers: sampled indices + per-proof flags; the host-buffer forms' uploads
+    WS_INV,           // multi_inv / multi_interp_4: the tile products of the levels above the items
     WS_COUNT
   };
   void* ws[WS_COUNT] = {};
@@ -1741,6 +1742,70 @@ int sh_fri_verify_batch(sh_ctx* c, const uint8_t* proofs, uint64_t proof_len, co
   SH_TRY(h2d(c, d + pbytes, merkle_roots, (size_t)batch * 32));
   SH_TRY(vb_launch(c, p, d, d + pbytes, nullptr, nullptr, 0, batch, d_status));
   return d2h(c, status, d_status, (size_t)batch * 4);
+}
+
+}  // extern "C"
+
+// ---- batch inversion and four-point interpolation (multi_inv.hip, inv_items.cuh) ------------------------------------------------------
+namespace {
+// [a, a + na) and [b, b + nb) share a byte but are not the same buffer
+bool partial_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 != b0 && a0 < b0 + nb && b0 < a0 + na;
+}
+constexpr uint64_t IV_MAX_ITEMS = 1ull << 52;  // keeps every byte count of a call far from 2^64
+
+int multi_inv_run(sh_ctx* c, const fp* in, fp* out, uint64_t n) {
+  void* s = nullptr;
+  SH_TRY(ws_get(c, sh_ctx::WS_INV, (size_t)shk_multi_inv_scratch(n) * sizeof(fp), &s));
+  HIP_TRY(c, shk_multi_inv(in, out, n, static_cast<fp*>(s), c->stream));
+  return SH_OK;
+}
+int multi_interp_4_run(sh_ctx* c, const fp* xs, const fp* ys, fp* coeffs, uint64_t rows) {
+  void* s = nullptr;
+  SH_TRY(ws_get(c, sh_ctx::WS_INV, (size_t)shk_multi_interp_4_scratch(rows) * sizeof(fp), &s));
+  HIP_TRY(c, shk_multi_interp_4(xs, ys, coeffs, rows, static_cast<fp*>(s), c->stream));
+  return SH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sh_dev_multi_inv(sh_ctx* c, const void* d_in, void* d_out, uint64_t n) {
+  if (!c || !d_in || !d_out || n > IV_MAX_ITEMS || partial_overlap(d_in, 32 * n, d_out, 32 * n)) return SH_ERR_INVALID;
+  if (n == 0) return SH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return multi_inv_run(c, static_cast<const fp*>(d_in), static_cast<fp*>(d_out), n);
+}
+
+int sh_multi_inv(sh_ctx* c, const uint8_t* in, uint64_t n, uint8_t* out) {
+  if (!c || !in || !out || n > IV_MAX_ITEMS) return SH_ERR_INVALID;
+  if (n == 0) return SH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  fp* x = nullptr;
+  SH_TRY(upload_padded(c, in, n, n, 1, sh_ctx::WS_X, &x));
+  SH_TRY(multi_inv_run(c, x, x, n));
+  return download_wire(c, x, out, n);
+}
+
+int sh_dev_multi_interp_4(sh_ctx* c, const void* d_xs, const void* d_ys, uint64_t rows, void* d_coeffs) {
+  if (!c || !d_xs || !d_ys || !d_coeffs || rows > IV_MAX_ITEMS) return SH_ERR_INVALID;
+  const uint64_t bytes = 128 * rows;
+  if (partial_overlap(d_xs, bytes, d_coeffs, bytes) || partial_overlap(d_ys, bytes, d_coeffs, bytes)) return SH_ERR_INVALID;
+  if (rows == 0) return SH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return multi_interp_4_run(c, static_cast<const fp*>(d_xs), static_cast<const fp*>(d_ys), static_cast<fp*>(d_coeffs), rows);
+}
+
+int sh_multi_interp_4(sh_ctx* c, const uint8_t* xs, const uint8_t* ys, uint64_t rows, uint8_t* coeffs) {
+  if (!c || !xs || !ys || !coeffs || rows > IV_MAX_ITEMS) return SH_ERR_INVALID;
+  if (rows == 0) return SH_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  fp *x = nullptr, *y = nullptr;
+  SH_TRY(upload_padded(c, xs, 4 * rows, 4 * rows, 1, sh_ctx::WS_X, &x));
+  SH_TRY(upload_padded(c, ys, 4 * rows, 4 * rows, 1, sh_ctx::WS_Y, &y));
+  SH_TRY(multi_interp_4_run(c, x, y, x, rows));
+  return download_wire(c, x, coeffs, 4 * rows);
 }
 
 }  // extern "C"

@@ -166,3 +166,12 @@ hipError_t shk_stark_scalars(const uint32_t* d_mnodes, uint64_t tree_words, uint
 hipError_t shk_stark_lincomb_tree(const StarkArgs& a, const fp* d_scal, fp* d_l, uint32_t* d_lnodes, hipStream_t st);
 hipError_t shk_stark_gather(const StarkArgs& a, const uint32_t* d_mnodes, const uint32_t* d_lnodes, const fp* d_lvals,
                             const uint32_t* d_ys, uint32_t samples, uint8_t* d_proof, uint64_t stride, hipStream_t st);
+
+// ---- multi_inv.hip: batch inversion and four-point interpolation (poly_utils.py:301-320, 412-440; inv_items.cuh) ----------------
+// scratch: shk_multi_inv_scratch(n) / shk_multi_interp_4_scratch(rows) elements (0 when the items fit one tile)
+uint64_t shk_multi_inv_scratch(uint64_t n);
+uint64_t shk_multi_interp_4_scratch(uint64_t rows);
+// out[i] = in[i]^-1, 0 for in[i] == 0 mod p; in may equal out; n >= 1
+hipError_t shk_multi_inv(const fp* in, fp* out, uint64_t n, fp* scratch, hipStream_t st);
+// xs, ys, coeffs: [rows][4]; coeffs may equal xs or ys; rows >= 1
+hipError_t shk_multi_interp_4(const fp* xs, const fp* ys, fp* coeffs, uint64_t rows, fp* scratch, hipStream_t st);

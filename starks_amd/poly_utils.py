@@ -1,0 +1,133 @@
+"""Batch inversion and four-point interpolation on the MI355X behind the reference's call sites (starks/poly_utils.py:301-320,
+412-440):
+
+    multi_inv(field, values) -> sequence              (one field inversion for all values)
+    multi_interp_4(field, xsets, ysets) -> [Poly]      (the cubic through each row's four points)
+    multi_inv_wire(data) -> bytes, multi_interp_4_wire(xs, ys, rows) -> bytes   (wire form in and out, for large inputs)
+
+For the MiMC prime both always run on the GPU through libstarkhip.so (sh_multi_inv, sh_multi_interp_4) and raise when the library
+or the device is missing: there is no CPU fallback for them.  Another modulus (the reference's own tests use Z/7) is outside the hot
+path: there the reference's algorithm runs on the host on the field's own elements, as fft._host_dft does for transforms.
+
+The reference's multi_inv tests the truthiness of each value (poly_utils.py:317): a zero Python int comes back as 0, a zero FIELD
+ELEMENT -- always truthy -- as 1.  The device computes 0 for every zero; `multi_inv` puts the 1 back where the input was an element
+(a WireList holds elements), so both forms give what the reference gives.  multi_interp_4 hands the reference's multi_inv field
+elements only, so a row with a repeated x has e_k = 0 "inverted" to 1; the device does the same (include/starkhip.h).
+"""
+import ctypes
+
+from . import _lib
+from ._lib import MIMC_P
+from .polynomial import polynomials_over
+from .wireseq import WireList
+
+
+def _on_device(field):
+    return int(getattr(field, "p", 0)) == MIMC_P
+
+
+def multi_inv_wire(data):
+    """n 32-byte big-endian values (may be >= p) -> their n inverses, canonical, 0 for a value == 0 mod p (sh_multi_inv)."""
+    data = bytes(data) if not isinstance(data, bytes) else data
+    if len(data) % 32:
+        raise ValueError("wire form is a multiple of 32 bytes")
+    n = len(data) // 32
+    if n == 0:
+        return b""
+    out = ctypes.create_string_buffer(32 * n)
+    _lib.check(_lib.lib().sh_multi_inv(_lib.ctx(), data, n, out), "sh_multi_inv")
+    return out.raw
+
+
+def multi_interp_4_wire(xs, ys, rows):
+    """xs, ys: [rows][4] wire form -> [rows][4] coefficients (constant first), canonical wire form (sh_multi_interp_4)."""
+    xs = bytes(xs) if not isinstance(xs, bytes) else xs
+    ys = bytes(ys) if not isinstance(ys, bytes) else ys
+    if len(xs) != 128 * rows or len(ys) != 128 * rows:
+        raise ValueError("xs and ys must hold 4 * rows 32-byte values")
+    if rows == 0:
+        return b""
+    out = ctypes.create_string_buffer(128 * rows)
+    _lib.check(_lib.lib().sh_multi_interp_4(_lib.ctx(), xs, ys, rows, out), "sh_multi_interp_4")
+    return out.raw
+
+
+def _zero_rows(raw):
+    """indices of the all-zero 32-byte records of raw"""
+    import numpy as np
+    a = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 32)
+    return np.flatnonzero(~a.any(axis=1)).tolist()
+
+
+def multi_inv(field, values):
+    """starks/poly_utils.py:301-320: the inverse of every value, one field inversion in all."""
+    if not _on_device(field):
+        return _host_multi_inv(field, list(values))
+    elements = isinstance(values, WireList)
+    if not elements and not isinstance(values, (list, tuple)):
+        values = list(values)
+    out = multi_inv_wire(_lib.to_wire(values))
+    zeros = _zero_rows(out)  # an inverse is 0 exactly where the value is 0 mod p
+    if zeros:
+        buf = bytearray(out)
+        for i in zeros:
+            if elements or not isinstance(values[i], int):  # a zero field element is truthy (poly_utils.py:317): 1, not 0
+                buf[32 * i + 31] = 1
+        out = bytes(buf)
+    return WireList(out, field)
+
+
+def multi_interp_4(field, xsets, ysets):
+    """starks/poly_utils.py:412-440: for each row, the polynomial of degree < 4 through (xs[k], ys[k]), k < 4, as a polynomial
+    over `field` (trailing zero coefficients stripped, as polysOver does)."""
+    xsets, ysets = list(xsets), list(ysets)
+    if len(xsets) != len(ysets) or any(len(r) != 4 for r in xsets) or any(len(r) != 4 for r in ysets):
+        raise ValueError("multi_interp_4 takes rows of four x and four y values")
+    if not _on_device(field):
+        return _host_multi_interp_4(field, xsets, ysets)
+    rows = len(xsets)
+    raw = multi_interp_4_wire(b"".join(_lib.to_wire(list(r)) for r in xsets), b"".join(_lib.to_wire(list(r)) for r in ysets), rows)
+    coeffs = WireList(raw, field)
+    polys_over = polynomials_over(field)
+    return [polys_over(coeffs[4 * r:4 * r + 4]) for r in range(rows)]
+
+
+# ---- host forms for other moduli (never the MiMC field) ---------------------------------------------------------------------------
+def _host_multi_inv(field, values):
+    """The reference's algorithm on the field's own elements (poly_utils.py:301-320), its truthiness test included."""
+    partials = [field(1)]
+    for val in values:
+        partials.append(partials[-1] * (1 if val == 0 else val))
+    inv = field(1) / partials[-1]
+    outputs = [0] * len(values)
+    for i in range(len(values), 0, -1):
+        outputs[i - 1] = partials[i - 1] * inv if values[i - 1] else 0
+        if values[i - 1] != 0:
+            inv = inv * values[i - 1]
+    return outputs
+
+
+def _host_multi_interp_4(field, xsets, ysets):
+    """poly_utils.py:412-440 on the host: eq_k = prod_{j != k} (X - x_j) by its coefficients, e_k = eq_k(x_k), one _host_multi_inv
+    over every e_k, coefficients sum_k eq_k y_k / e_k."""
+    polys_over = polynomials_over(field)
+    data, targets = [], []
+    for xs, ys in zip(xsets, ysets):
+        xs = [field(v) if isinstance(v, int) else v for v in xs]
+        ys = [field(v) if isinstance(v, int) else v for v in ys]
+        eqs = []
+        for k in range(4):
+            a, b, c = [xs[j] for j in range(4) if j != k]
+            eqs.append([-(a * b * c), a * b + a * c + b * c, -(a + b + c), field(1)])
+        for k in range(4):
+            e = field(0)
+            for coef in reversed(eqs[k]):
+                e = e * xs[k] + coef
+            targets.append(e)
+        data.append((ys, eqs))
+    invs = _host_multi_inv(field, targets)
+    out = []
+    for r, (ys, eqs) in enumerate(data):
+        w = [ys[k] * invs[4 * r + k] for k in range(4)]
+        out.append(polys_over([eqs[0][i] * w[0] + eqs[1][i] * w[1] + eqs[2][i] * w[2] + eqs[3][i] * w[3] for i in range(4)]))
+    return out
