@@ -108,6 +108,14 @@ def lib():
         "sh_multi_inv": (i32, [c_p, u8p, u64, c_p]),
         "sh_dev_multi_interp_4": (i32, [c_p, c_p, c_p, u64, c_p]),
         "sh_multi_interp_4": (i32, [c_p, u8p, u8p, u64, c_p]),
+        "sh_dev_poly_mul": (i32, [c_p, c_p, u64, c_p, u64, c_p]),
+        "sh_poly_mul": (i32, [c_p, u8p, u64, u8p, u64, c_p]),
+        "sh_dev_poly_divmod": (i32, [c_p, c_p, u64, c_p, u64, c_p, c_p]),
+        "sh_poly_divmod": (i32, [c_p, u8p, u64, u8p, u64, c_p, c_p]),
+        "sh_dev_zpoly": (i32, [c_p, c_p, u64, c_p]),
+        "sh_zpoly": (i32, [c_p, u8p, u64, c_p]),
+        "sh_dev_lagrange_interp": (i32, [c_p, c_p, c_p, u64, c_p]),
+        "sh_lagrange_interp": (i32, [c_p, u8p, u8p, u64, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares

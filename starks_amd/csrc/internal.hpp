@@ -175,3 +175,18 @@ uint64_t shk_multi_interp_4_scratch(uint64_t rows);
 hipError_t shk_multi_inv(const fp* in, fp* out, uint64_t n, fp* scratch, hipStream_t st);
 // xs, ys, coeffs: [rows][4]; coeffs may equal xs or ys; rows >= 1
 hipError_t shk_multi_interp_4(const fp* xs, const fp* ys, fp* coeffs, uint64_t rows, fp* scratch, hipStream_t st);
+
+// ---- poly_arith.hip: products, division, zpoly, lagrange_interp (polynomial.py:116-150, poly_utils.py:322-369; poly_items.cuh) ----
+#include "poly_items.cuh"
+hipError_t shk_pa_copy(const PaCopy& c, const fp* src, fp* dst, hipStream_t st);
+// hz: [nodes][2^log2d] transformed Z-nodes -> oz [nodes/2][2^log2d] (parents, before the inverse transform); hn / on the same for
+// the numerators (either pair may be null)
+hipError_t shk_pa_tree(const fp* hz, fp* oz, const fp* hn, fp* on, uint32_t log2d, uint64_t nodes, hipStream_t st);
+// hd: [children/2][2^log2d] transformed parent remainders; hr: [children][2^log2d] transformed rev(Z) of the children, replaced
+// in place by parent * sibling
+hipError_t shk_pa_mid(const fp* hd, fp* hr, uint32_t log2d, uint64_t children, hipStream_t st);
+hipError_t shk_pa_newton(const fp* F, fp* G, uint64_t n, hipStream_t st);
+hipError_t shk_pa_inv1(const fp* src, fp* dst, hipStream_t st);
+hipError_t shk_pa_deriv_rev(const fp* top, fp* out, uint64_t N, uint64_t n, hipStream_t st);
+hipError_t shk_pa_weights(const fp* ys, const fp* inv, fp* out, uint64_t n, uint64_t N, hipStream_t st);
+hipError_t shk_pa_sub(const fp* a, const fp* b, fp* out, uint64_t n, hipStream_t st);

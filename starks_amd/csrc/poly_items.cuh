@@ -1,0 +1,267 @@
+// poly_items.cuh -- the per-element and per-node steps of univariate polynomial arithmetic on the device (poly_arith.hip, driven
+// from capi.hip): exact products, division with remainder, zpoly and lagrange_interp (starks/polynomial.py:116-150,
+// starks/poly_utils.py:322-369), all built from batched cyclic NTTs of power-of-two sizes.
+//
+// Product tree.  n points are padded with zeros to N = 2^lg points (a zero point adds a factor X, which the callers shift out
+// again).  A node of degree d is monic and stored as its d lower coefficients a, the leading 1 implicit.  Two siblings multiply
+// without wrap-around in a cyclic convolution of size 2d:
+//     (X^d + a)(X^d + b) = X^2d + X^d (a + b) + ab,     deg ab <= 2d - 2,
+// and in the size-2d transform X^d is (w^d)^i = (-1)^i, so the parent's 2d lower coefficients are the inverse transform of
+// A B + (-1)^i (A + B) (pa_tree_node).  A level of the tree is two batched forward transforms (one of them shared when both
+// siblings sit in one batch), one pointwise launch and one batched inverse transform.
+//
+// Numerators.  N_v = N_L Z_R + N_R Z_L with deg N < d: in the same size-2d transform N_L (X^d + b) is N_L (B + (-1)^i)
+// (pa_num_node).  At the leaves N = w_i, at the top N = sum_i w_i prod_{j != i} (X - x_j).
+//
+// Multipoint evaluation (Bernstein's scaled remainder tree).  For P with deg P < N and Z = prod (X - x_i), the fractional part
+// of P / Z_v at a node v is y D_v(y), y = 1/X, where D_v holds |v| coefficients.  At the root D = rev_{N-1}(P) rev(Z)^-1 mod y^N
+// (one Newton inverse); a child c with sibling s takes D_c[k] = (D_v rev(Z_s))[d + k], k < d, the middle of a product that a
+// size-2d cyclic convolution leaves intact (pa_mid); at a leaf D = P(x_i).  rev(Z_s) = 1 + a_{d-1} y + ... + a_0 y^d
+// (pa_copy with PA_ONE_AT_END: the implicit leading 1).
+//
+// Division.  q = rev(rev(a) rev(b)^-1 mod X^(m-k+1)), the inverse by Newton's iteration g <- g (2 - f g) (pa_newton), then
+// r = a - q b on the low k - 1 coefficients.
+//
+// The element steps are __host__ __device__, and the drivers below are templates over an Ops back end that supplies the
+// transforms and the per-level launches: capi.hip's runs batched NTT plans and the poly_arith.hip kernels on the ctx stream,
+// tests/native/poly_tree_host.cpp's a textbook NTT and loops, so the host test runs this very driver and checks it against exact
+// integers.
+#pragma once
+#include <stdint.h>
+
+#include "fp256.cuh"
+
+FP_HD fp pa_ld(const fp* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return fp_load(p);
+#else
+  return *p;
+#endif
+}
+
+// Z-node of the parent at transform index i: A B + (-1)^i (A + B)
+FP_HD fp pa_tree_node(const fp& A, const fp& B, uint64_t i) {
+  const fp ab = fp_mul(A, B), s = fp_add(A, B);
+  return (i & 1) ? fp_sub(ab, s) : fp_add(ab, s);
+}
+
+// numerator of the parent at transform index i: N_A (B + (-1)^i) + N_B (A + (-1)^i)
+FP_HD fp pa_num_node(const fp& NA, const fp& NB, const fp& A, const fp& B, uint64_t i) {
+  const fp one = fp_one();
+  const fp b1 = (i & 1) ? fp_sub(B, one) : fp_add(B, one);
+  const fp a1 = (i & 1) ? fp_sub(A, one) : fp_add(A, one);
+  return fp_add(fp_mul(NA, b1), fp_mul(NB, a1));
+}
+
+// one Newton step of the power-series inverse in the transform domain: G (2 - F G)
+FP_HD fp pa_newton(const fp& F, const fp& G) {
+  const fp fg = fp_mul(F, G);
+  return fp_mul(G, fp_sub(fp_from_u32(2u), fg));
+}
+
+// A strided, optionally reversed copy of rows: dst[r * ds + k] = v(off + dir * k) for k < len, where v(s) = src[r * ss + s] for
+// 0 <= s < src_len, 1 at s == src_len when PA_ONE_AT_END (a monic node's implicit leading coefficient), 0 elsewhere; PA_NEG
+// negates, PA_CANON stores the canonical residue.
+enum : uint32_t { PA_NEG = 1u, PA_ONE_AT_END = 2u, PA_CANON = 4u };
+struct PaCopy {
+  uint64_t rows, len;     // rows x len outputs
+  uint64_t ss, ds;        // row strides of src and dst (elements)
+  uint64_t src_len;       // valid elements per source row
+  int64_t off;            // source index of output 0
+  int32_t dir;            // +1 or -1
+  uint32_t flags;
+};
+
+FP_HD fp pa_copy_item(const PaCopy& c, const fp* src, uint64_t r, uint64_t k) {
+  const int64_t s = c.off + (int64_t)c.dir * (int64_t)k;
+  fp v = fp_zero();
+  if (s >= 0 && (uint64_t)s < c.src_len) v = pa_ld(src + r * c.ss + (uint64_t)s);
+  else if ((c.flags & PA_ONE_AT_END) && s >= 0 && (uint64_t)s == c.src_len) v = fp_one();
+  if (c.flags & PA_NEG) v = fp_neg(fp_canon(v));
+  if (c.flags & PA_CANON) v = fp_canon(v);
+  return v;
+}
+
+// rev_{N-1}(Z')[k], Z = the true product of the first n points: Z[m] = top[m + N - n] for m < n, Z[n] = 1, where top holds the N
+// lower coefficients of the padded product X^(N-n) Z.  Z'[m] = (m + 1) Z[m + 1], so rev[k] = Z'[N-1-k] = (N - k) Z[N - k], zero
+// where N - 1 - k >= n.
+FP_HD fp pa_deriv_rev(const fp* top, uint64_t N, uint64_t n, uint64_t k) {
+  const uint64_t m = N - k;  // index into Z, 1 <= m <= N
+  if (m > n) return fp_zero();
+  const fp z = m == n ? fp_one() : pa_ld(top + m + N - n);
+  return fp_mul(fp_from_u32((uint32_t)m), z);
+}
+
+// the weight of point i: y_i / d_i, where a zero d_i (a repeated x) counts as 1 -- what the reference's multi_inv returns for a
+// zero field element (poly_utils.py:317); inv = multi_inv(d) is 0 exactly there
+FP_HD fp pa_weight(const fp& y, const fp& inv) {
+  const fp ic = fp_canon(inv);
+  return fp_eq_canon(ic, fp_zero()) ? y : fp_mul(y, ic);
+}
+
+// ---- the drivers -------------------------------------------------------------------------------------------------------------------
+// Ops: int ntt(src, dst, batch, n, n_in, inverse)  [batch][n] size-n cyclic transforms over 7^((p - 1) / n) of [batch][n_in] inputs
+//                                                  (zero beyond; n_in = 0: n), the inverse scaled by 1/n; src may equal dst when n_in = 0
+//      int copy(PaCopy, src, dst), pointwise(a, b, out, n), tree(hz, oz, hn, on, log2d, nodes), mid(hd, hr, log2d, children),
+//      newton(F, G, n), inv1(src, dst), deriv_rev(top, out, N, n), multi_inv(in, out, n), weights(ys, inv, out, n, N), sub(a, b, out, n)
+//      int buf(slot, elems, fp**)                      scratch that stays valid for the call (one request per slot per call)
+// Every call returns 0 or an error code, which the drivers pass on.
+#define PA_TRY(expr)           \
+  do {                         \
+    const int rc_ = (expr);    \
+    if (rc_ != 0) return rc_;  \
+  } while (0)
+
+enum : int { PA_BUF_TREE = 0, PA_BUF_1, PA_BUF_2, PA_BUF_3, PA_BUF_4, PA_BUF_5, PA_BUF_COUNT };
+
+inline uint64_t pa_pow2_at_least(uint64_t n) {
+  uint64_t s = 2;
+  while (s < n) s <<= 1;
+  return s;
+}
+inline uint32_t pa_log2(uint64_t n) {
+  uint32_t k = 0;
+  while ((1ull << k) < n) ++k;
+  return k;
+}
+template <class Ops>
+int pa_cp(Ops& o, const fp* src, fp* dst, uint64_t rows, uint64_t len, uint64_t ss, uint64_t ds, uint64_t src_len, int64_t off, int dir,
+          uint32_t flags) {
+  return o.copy(PaCopy{rows, len, ss, ds, src_len, off, (int32_t)dir, flags}, src, dst);
+}
+
+// out[0, na + nb - 1) = a b, canonical; na, nb >= 1; out must not alias a or b; t1, t2: pa_pow2_at_least(na + nb - 1) elements each
+template <class Ops>
+int pa_mul(Ops& o, const fp* a, uint64_t na, const fp* b, uint64_t nb, fp* out, fp* t1, fp* t2) {
+  const uint64_t nc = na + nb - 1, S = pa_pow2_at_least(nc);
+  PA_TRY(o.ntt(a, t1, 1, S, na, false));
+  PA_TRY(o.ntt(b, t2, 1, S, nb, false));
+  PA_TRY(o.pointwise(t1, t2, t1, S));
+  PA_TRY(o.ntt(t1, t1, 1, S, 0, true));
+  return pa_cp(o, t1, out, 1, nc, 0, 0, nc, 0, 1, PA_CANON);
+}
+
+// elements t1 and t2 of pa_inverse need for L coefficients
+inline uint64_t pa_inverse_scratch(uint64_t L) { return 2 * pa_pow2_at_least(L); }
+// g[0, L) = f^-1 mod X^L by Newton's iteration (precision 1, 2, 4, ..., L); f is given by its first nf >= 1 coefficients, f[0] != 0
+template <class Ops>
+int pa_inverse(Ops& o, const fp* f, uint64_t nf, uint64_t L, fp* g, fp* t1, fp* t2) {
+  PA_TRY(o.inv1(f, g));
+  for (uint64_t m = 1; m < L; m *= 2) {
+    const uint64_t m2 = 2 * m < L ? 2 * m : L, S = pa_pow2_at_least(2 * m + m2 - 2);  // deg g^2 f < 2m + m2 - 2: no wrap-around
+    PA_TRY(o.ntt(f, t1, 1, S, nf < m2 ? nf : m2, false));
+    PA_TRY(o.ntt(g, t2, 1, S, m, false));
+    PA_TRY(o.newton(t1, t2, S));
+    PA_TRY(o.ntt(t2, t2, 1, S, 0, true));
+    PA_TRY(pa_cp(o, t2, g, 1, m2, 0, 0, m2, 0, 1, 0));
+  }
+  return 0;
+}
+
+// q[0, na - nb + 1) and r[0, nb - 1) with a = q b + r (na >= nb); or, for na < nb, q empty and r[0, na) = a.  b[nb - 1] != 0 mod p.
+template <class Ops>
+int pa_divmod(Ops& o, const fp* a, uint64_t na, const fp* b, uint64_t nb, fp* q, fp* r) {
+  if (na < nb) return pa_cp(o, a, r, 1, na, 0, 0, na, 0, 1, PA_CANON);
+  const uint64_t L = na - nb + 1, lb = nb < L ? nb : L;
+  uint64_t S = pa_inverse_scratch(L);
+  if (pa_pow2_at_least(2 * L - 1) > S) S = pa_pow2_at_least(2 * L - 1);
+  if (pa_pow2_at_least(na) > S) S = pa_pow2_at_least(na);
+  fp *t1, *t2, *w, *qb;
+  PA_TRY(o.buf(PA_BUF_1, S, &t1));
+  PA_TRY(o.buf(PA_BUF_2, S, &t2));
+  PA_TRY(o.buf(PA_BUF_3, 5 * L, &w));
+  PA_TRY(o.buf(PA_BUF_4, na, &qb));
+  fp *ra = w, *rb = w + L, *g = w + 2 * L, *qr = w + 3 * L;  // qr: 2L - 1
+  PA_TRY(pa_cp(o, a, ra, 1, L, 0, 0, na, (int64_t)na - 1, -1, 0));   // rev(a) mod X^L
+  PA_TRY(pa_cp(o, b, rb, 1, lb, 0, 0, nb, (int64_t)nb - 1, -1, 0));  // rev(b) mod X^L
+  PA_TRY(pa_inverse(o, rb, lb, L, g, t1, t2));
+  PA_TRY(pa_mul(o, ra, L, g, L, qr, t1, t2));
+  PA_TRY(pa_cp(o, qr, q, 1, L, 0, 0, L, (int64_t)L - 1, -1, PA_CANON));
+  if (nb == 1) return 0;
+  PA_TRY(pa_mul(o, q, L, b, nb, qb, t1, t2));
+  return o.sub(a, qb, r, nb - 1);
+}
+
+// level j of a product tree over N points: [N >> j] monic nodes of degree 2^j, their 2^j lower coefficients each
+inline fp* pa_level(fp* tree, uint64_t N, uint32_t j, bool keep) { return tree + (keep ? j : (j & 1)) * N; }
+
+// the product tree of x_0 .. x_{n-1} padded with zeros to N points; keep: every level in tree[(lg + 1) N], else two alternating
+// levels in tree[2N] (the top is pa_level(tree, N, lg, keep)); hat: 2N elements
+template <class Ops>
+int pa_tree_up(Ops& o, const fp* xs, uint64_t n, uint64_t N, fp* tree, bool keep, fp* hat) {
+  const uint32_t lg = pa_log2(N);
+  PA_TRY(pa_cp(o, xs, pa_level(tree, N, 0, keep), 1, N, 0, 0, n, 0, 1, PA_NEG));  // X - x_i, X beyond n
+  for (uint32_t j = 0; j < lg; ++j) {
+    const uint64_t d = 1ull << j, nodes = N >> j;
+    fp *lo = pa_level(tree, N, j, keep), *up = pa_level(tree, N, j + 1, keep);
+    PA_TRY(o.ntt(lo, hat, nodes, 2 * d, d, false));
+    PA_TRY(o.tree(hat, up, nullptr, nullptr, j + 1, nodes));
+    PA_TRY(o.ntt(up, up, nodes / 2, 2 * d, 0, true));
+  }
+  return 0;
+}
+
+// out[0, n + 1) = prod (X - x_i), leading 1
+template <class Ops>
+int pa_zpoly(Ops& o, const fp* xs, uint64_t n, fp* out) {
+  if (n == 0) return pa_cp(o, nullptr, out, 1, 1, 0, 0, 0, 0, 1, PA_ONE_AT_END);
+  const uint64_t N = pa_pow2_at_least(n);
+  fp *tree, *hat;
+  PA_TRY(o.buf(PA_BUF_TREE, 2 * N, &tree));
+  PA_TRY(o.buf(PA_BUF_3, 2 * N, &hat));
+  PA_TRY(pa_tree_up(o, xs, n, N, tree, false, hat));
+  // the padded product is X^(N - n) Z: Z's coefficients are the top's from N - n on, and the implicit 1
+  return pa_cp(o, pa_level(tree, N, pa_log2(N), false), out, 1, n + 1, 0, 0, N, (int64_t)(N - n), 1, PA_ONE_AT_END | PA_CANON);
+}
+
+// out[0, n) = sum_i y_i w_i prod_{j != i} (X - x_j), w_i = 1 / Z'(x_i), or 1 where Z'(x_i) = 0 (poly_utils.py:337-369); n >= 1
+template <class Ops>
+int pa_lagrange(Ops& o, const fp* xs, const fp* ys, uint64_t n, fp* out) {
+  const uint64_t N = pa_pow2_at_least(n);
+  const uint32_t lg = pa_log2(N);
+  fp *tree, *hat, *t1, *t2, *r;
+  PA_TRY(o.buf(PA_BUF_TREE, (lg + 1) * N, &tree));
+  PA_TRY(o.buf(PA_BUF_3, 2 * N, &hat));
+  PA_TRY(o.buf(PA_BUF_1, 2 * N, &t1));
+  PA_TRY(o.buf(PA_BUF_2, 2 * N, &t2));
+  PA_TRY(o.buf(PA_BUF_5, 4 * N, &r));
+  fp* R[4] = {r, r + N, r + 2 * N, r + 3 * N};
+  PA_TRY(pa_tree_up(o, xs, n, N, tree, true, hat));
+  const fp* top = pa_level(tree, N, lg, true);
+  // the root of the scaled remainder tree: D = rev_{N-1}(Z') rev(Z)^-1 mod y^N; rev(Z)[k] = Z[N - k] (1 at k = 0)
+  PA_TRY(pa_cp(o, top, R[2], 1, N, 0, 0, N, (int64_t)N, -1, PA_ONE_AT_END));
+  PA_TRY(pa_inverse(o, R[2], N, N, R[0], t1, t2));
+  PA_TRY(o.deriv_rev(top, R[1], N, n));
+  PA_TRY(pa_mul(o, R[1], N, R[0], N, hat, t1, t2));  // 2N - 1 coefficients, the low N are D
+  PA_TRY(pa_cp(o, hat, R[2], 1, N, 0, 0, N, 0, 1, 0));
+  fp *dcur = R[2], *dnext = R[3];
+  for (int j = (int)lg - 1; j >= 0; --j) {
+    const uint64_t d = 1ull << j, children = N >> j;
+    PA_TRY(o.ntt(dcur, t1, children / 2, 2 * d, 0, false));
+    // rev(Z_c) = 1 + a_{d-1} y + ... + a_0 y^d of every child
+    PA_TRY(pa_cp(o, pa_level(tree, N, (uint32_t)j, true), t2, children, d + 1, d, d + 1, d, (int64_t)d, -1, PA_ONE_AT_END));
+    PA_TRY(o.ntt(t2, hat, children, 2 * d, d + 1, false));
+    PA_TRY(o.mid(t1, hat, (uint32_t)j + 1, children));
+    PA_TRY(o.ntt(hat, hat, children, 2 * d, 0, true));
+    PA_TRY(pa_cp(o, hat, dnext, children, d, 2 * d, d, 2 * d, (int64_t)d, 1, 0));  // the middle: coefficients [d, 2d)
+    fp* t = dcur;
+    dcur = dnext;
+    dnext = t;
+  }
+  // dcur[i] = Z'(x_i) = prod_{j != i} (x_i - x_j); the weights y_i / Z'(x_i) are the leaves of the numerator tree
+  PA_TRY(o.multi_inv(dcur, t1, n));
+  PA_TRY(o.weights(ys, t1, R[0], n, N));
+  fp *ncur = R[0], *nnext = R[1];
+  for (uint32_t j = 0; j < lg; ++j) {
+    const uint64_t d = 1ull << j, nodes = N >> j;
+    PA_TRY(o.ntt(pa_level(tree, N, j, true), hat, nodes, 2 * d, d, false));
+    PA_TRY(o.ntt(ncur, t1, nodes, 2 * d, d, false));
+    PA_TRY(o.tree(hat, nullptr, t1, nnext, j + 1, nodes));
+    PA_TRY(o.ntt(nnext, nnext, nodes / 2, 2 * d, 0, true));
+    fp* t = ncur;
+    ncur = nnext;
+    nnext = t;
+  }
+  // the padded numerator is X^(N - n) times the true one
+  return pa_cp(o, ncur, out, 1, n, 0, 0, N, (int64_t)(N - n), 1, PA_CANON);
+}

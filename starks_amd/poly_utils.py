@@ -1,9 +1,12 @@
-"""Batch inversion and four-point interpolation on the MI355X behind the reference's call sites (starks/poly_utils.py:301-320,
-412-440):
+"""Batch inversion, four-point interpolation, zpoly and Lagrange interpolation on the MI355X behind the reference's call sites
+(starks/poly_utils.py:301-369, 412-440):
 
     multi_inv(field, values) -> sequence              (one field inversion for all values)
     multi_interp_4(field, xsets, ysets) -> [Poly]      (the cubic through each row's four points)
-    multi_inv_wire(data) -> bytes, multi_interp_4_wire(xs, ys, rows) -> bytes   (wire form in and out, for large inputs)
+    zpoly(field, roots) -> Poly                        (prod (X - x_i): a product tree of batched NTTs, O(n log^2 n))
+    lagrange_interp(field, xs, ys) -> Poly             (the reference's interpolant, O(n log^2 n) instead of its O(n^3))
+    multi_inv_wire(data) -> bytes, multi_interp_4_wire(xs, ys, rows) -> bytes,
+    zpoly_wire(xs) -> bytes, lagrange_interp_wire(xs, ys) -> bytes   (wire form in and out, for large inputs)
 
 For the MiMC prime both always run on the GPU through libstarkhip.so (sh_multi_inv, sh_multi_interp_4) and raise when the library
 or the device is missing: there is no CPU fallback for them.  Another modulus (the reference's own tests use Z/7) is outside the hot
@@ -92,6 +95,51 @@ def multi_interp_4(field, xsets, ysets):
     return [polys_over(coeffs[4 * r:4 * r + 4]) for r in range(rows)]
 
 
+def zpoly_wire(xs):
+    """n 32-byte big-endian values (may be >= p) -> the n + 1 coefficients of prod (X - x_i), constant first, canonical (sh_zpoly)."""
+    xs = bytes(xs) if not isinstance(xs, bytes) else xs
+    if len(xs) % 32:
+        raise ValueError("wire form is a multiple of 32 bytes")
+    n = len(xs) // 32
+    out = ctypes.create_string_buffer(32 * (n + 1))
+    _lib.check(_lib.lib().sh_zpoly(_lib.ctx(), xs, n, out), "sh_zpoly")
+    return out.raw
+
+
+def lagrange_interp_wire(xs, ys):
+    """n x and n y values in wire form -> the n coefficients (constant first, canonical, not trimmed) of the reference's
+    lagrange_interp (sh_lagrange_interp), repeated x's included."""
+    xs = bytes(xs) if not isinstance(xs, bytes) else xs
+    ys = bytes(ys) if not isinstance(ys, bytes) else ys
+    if len(xs) % 32 or len(ys) != len(xs):
+        raise ValueError("xs and ys must hold the same number of 32-byte values")
+    n = len(xs) // 32
+    if n == 0:
+        return b""
+    out = ctypes.create_string_buffer(32 * n)
+    _lib.check(_lib.lib().sh_lagrange_interp(_lib.ctx(), xs, ys, n, out), "sh_lagrange_interp")
+    return out.raw
+
+
+def zpoly(field, roots):
+    """starks/poly_utils.py:322-335: the monic polynomial whose roots are `roots` (the reference's debug print is not kept)."""
+    polys_over = polynomials_over(field)
+    if not _on_device(field):
+        return polys_over(_host_zpoly(field, list(roots)))
+    return polys_over(WireList(zpoly_wire(_lib.to_wire(roots)), field))
+
+
+def lagrange_interp(field, xs, ys):
+    """starks/poly_utils.py:337-369: sum_i y_i / d_i prod_{j != i} (X - x_j), d_i = prod_{j != i} (x_i - x_j), where a zero d_i (a
+    repeated x) counts as 1, as the reference's multi_inv has it for field elements (poly_utils.py:317)."""
+    xs, ys = list(xs), list(ys)
+    assert len(xs) == len(ys)  # the reference: assert len(root) == len(ys) + 1
+    polys_over = polynomials_over(field)
+    if not _on_device(field):
+        return _host_lagrange_interp(field, xs, ys)
+    return polys_over(WireList(lagrange_interp_wire(_lib.to_wire(xs), _lib.to_wire(ys)), field))
+
+
 # ---- host forms for other moduli (never the MiMC field) ---------------------------------------------------------------------------
 def _host_multi_inv(field, values):
     """The reference's algorithm on the field's own elements (poly_utils.py:301-320), its truthiness test included."""
@@ -131,3 +179,30 @@ def _host_multi_interp_4(field, xsets, ysets):
         w = [ys[k] * invs[4 * r + k] for k in range(4)]
         out.append(polys_over([eqs[0][i] * w[0] + eqs[1][i] * w[1] + eqs[2][i] * w[2] + eqs[3][i] * w[3] for i in range(4)]))
     return out
+
+
+def _host_zpoly(field, roots):
+    """poly_utils.py:322-335 on the field's own elements"""
+    root = [field(1)]
+    for x in roots:
+        root.insert(0, field(0))
+        for j in range(len(root) - 1):
+            root[j] -= root[j + 1] * x
+    return root
+
+
+def _host_lagrange_interp(field, xs, ys):
+    """poly_utils.py:337-369 on the host: the reference's numerators by long division of zpoly, denominators through its multi_inv"""
+    polys_over = polynomials_over(field)
+    root = polys_over(_host_zpoly(field, xs))
+    nums = [root / polys_over([-x, 1]) for x in xs]
+    denoms = [nums[i](xs[i]) for i in range(len(xs))]
+    invdenoms = _host_multi_inv(field, denoms)
+    b = [0 for _ in ys]
+    for i in range(len(xs)):
+        yslice = ys[i] * invdenoms[i]
+        num_coefficients = nums[i].coefficients
+        for j in range(len(ys)):
+            if num_coefficients[j] and ys[i]:
+                b[j] += num_coefficients[j] * yslice
+    return polys_over(b)

@@ -1,6 +1,15 @@
-"""Minimal dense univariate polynomial, enough for the hot path's boundary: `NonBinaryFFT.fft` takes one
-(its `.coefficients`, trailing zeros stripped) and `.inv_fft` returns one (starks/fft.py:263-272,
-starks/polynomial.py:13-21,58,158-164).  Schoolbook multiplication / division are out of scope."""
+"""Dense univariate polynomials over a ring (starks/polynomial.py): what `NonBinaryFFT.fft` takes and `.inv_fft` returns
+(starks/fft.py:263-272), with the reference's arithmetic -- `+ - * divmod / % **`, ints and ring elements cast to polynomials as
+its `typecheck` does (numbertype.py:31-54).
+
+Over the MiMC field every product and division runs on the GPU at every size (sh_poly_mul, sh_poly_divmod: NTT products and a
+Newton inverse, O(n log n)); the result is backed by the device's bytes (a WireList, trailing zeros stripped on the bytes).  Any
+other ring (the reference's own tests use Z/5, Z/7, Z/11 and Fraction) runs the reference's schoolbook algorithms on the host.
+Errors are the reference's: `/` and `%` by the zero polynomial raise ZeroDivisionError, `divmod` by it raises IndexError (the
+reference reads the divisor's leading coefficient, polynomial.py:131)."""
+import ctypes
+from itertools import zip_longest
+
 from .wireseq import WireList
 
 _POLYS = {}
@@ -75,7 +84,145 @@ def polynomials_over(ring):
             return "0" if self.is_zero() else " + ".join(
                 ("%s *x**%d" % (a, i)) if i else "%s" % a for i, a in enumerate(self.coefficients))
 
+        def leading_coefficient(self):
+            return self.coefficients[-1]
+
+        # ---- arithmetic (polynomial.py:84-150, numbertype.py:68-84) --------------------------------------------------------
+        def __neg__(self):
+            return Polynomial([-a for a in self.coefficients])
+
+        def __add__(self, other):
+            other = _cast(other)
+            zero = ring(0)
+            return Polynomial([x + y for x, y in zip_longest(self.coefficients, other.coefficients, fillvalue=zero)])
+
+        __radd__ = __add__
+
+        def __sub__(self, other):
+            return self + (-_cast(other))
+
+        def __rsub__(self, other):
+            return _cast(other) + (-self)
+
+        def __mul__(self, other):
+            other = _cast(other)
+            if self.is_zero() or other.is_zero():
+                return Polynomial([])
+            if _on_device(ring):
+                return Polynomial(WireList(mul_wire(_wire(self), _wire(other)), ring))
+            out = [ring(0) for _ in range(len(self) + len(other) - 1)]
+            for i, a in enumerate(self.coefficients):
+                for j, b in enumerate(other.coefficients):
+                    out[i + j] += a * b
+            return Polynomial(out)
+
+        __rmul__ = __mul__
+
+        def __divmod__(self, divisor):
+            divisor = _cast(divisor)
+            lc = divisor.leading_coefficient()  # IndexError for the zero polynomial, as in the reference
+            if _on_device(ring):
+                q, r = divmod_wire(_wire(self), _wire(divisor))
+                return Polynomial(WireList(q, ring)), Polynomial(WireList(r, ring))
+            quotient, remainder = Polynomial([]), self
+            deg = divisor.degree()
+            while remainder.degree() >= deg:
+                mono = Polynomial([ring(0)] * (remainder.degree() - deg) + [remainder.leading_coefficient() / lc])
+                quotient = quotient + mono
+                remainder = remainder - mono * divisor
+            return quotient, remainder
+
+        def __rdivmod__(self, other):
+            return divmod(_cast(other), self)
+
+        def __truediv__(self, divisor):
+            divisor = _cast(divisor)
+            if divisor.is_zero():
+                raise ZeroDivisionError
+            return divmod(self, divisor)[0]
+
+        def __rtruediv__(self, other):
+            return _cast(other) / self
+
+        def __mod__(self, divisor):
+            divisor = _cast(divisor)
+            if divisor.is_zero():
+                raise ZeroDivisionError
+            return divmod(self, divisor)[1]
+
+        def __rmod__(self, other):
+            return _cast(other) % self
+
+        def __pow__(self, n):  # square-and-multiply (numbertype.py:68-84)
+            if type(n) is not int:
+                raise TypeError
+            Q = self
+            R = self if n & 1 else Polynomial(1)
+            i = 2
+            while i <= n:
+                Q = Q * Q
+                if n & i == i:
+                    R = Q * R
+                i = i << 1
+            return R
+
+    def _cast(other):
+        """numbertype.typecheck: anything else is cast to a polynomial, and a failed cast is a TypeError"""
+        if isinstance(other, Polynomial):
+            return other
+        try:
+            return Polynomial(other)
+        except Exception as e:
+            raise TypeError("Not able to typecast %r of type %s to type %s: %s" % (other, type(other).__name__,
+                                                                                      Polynomial.__name__, e))
+
     Polynomial.ring = ring
+    Polynomial.operatorPrecedence = 2
     Polynomial.__name__ = "(%s)[x]" % ring.__name__
     _POLYS[ring] = Polynomial
     return Polynomial
+
+
+def _on_device(ring):
+    from ._lib import MIMC_P
+    return int(getattr(ring, "p", 0)) == MIMC_P
+
+
+def _wire(poly):
+    from . import _lib
+    return _lib.to_wire(poly.coefficients)
+
+
+def _as_bytes(data):
+    data = bytes(data) if not isinstance(data, bytes) else data
+    if len(data) % 32:
+        raise ValueError("wire form is a multiple of 32 bytes")
+    return data
+
+
+def mul_wire(a, b):
+    """The exact product of two coefficient vectors in wire form (ascending, values may be >= p) -> len(a) + len(b) - 1 canonical
+    coefficients, b"" when either is empty (sh_poly_mul).  Not trimmed."""
+    from . import _lib
+    a, b = _as_bytes(a), _as_bytes(b)
+    na, nb = len(a) // 32, len(b) // 32
+    if na == 0 or nb == 0:
+        return b""
+    out = ctypes.create_string_buffer(32 * (na + nb - 1))
+    _lib.check(_lib.lib().sh_poly_mul(_lib.ctx(), a, na, b, nb, out), "sh_poly_mul")
+    return out.raw
+
+
+def divmod_wire(a, b):
+    """(quotient, remainder) of a by b in wire form (sh_poly_divmod): max(len(a) - len(b) + 1, 0) and min(len(a), len(b) - 1)
+    canonical coefficients, not trimmed.  b's last coefficient must be nonzero mod p (else StarkHipError)."""
+    from . import _lib
+    a, b = _as_bytes(a), _as_bytes(b)
+    na, nb = len(a) // 32, len(b) // 32
+    if nb == 0:
+        raise ZeroDivisionError
+    nq, nr = max(na - nb + 1, 0), min(na, nb - 1)
+    q = ctypes.create_string_buffer(32 * max(nq, 1))
+    r = ctypes.create_string_buffer(32 * max(nr, 1))
+    _lib.check(_lib.lib().sh_poly_divmod(_lib.ctx(), a, na, b, nb, q, r), "sh_poly_divmod")
+    return q.raw[:32 * nq], r.raw[:32 * nr]
