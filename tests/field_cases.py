@@ -12,7 +12,8 @@ the condition the header's comment states, to take its branch.  `layouts` places
 import functools
 import os
 import random
-import subprocess
+
+import native_harness
 
 P = 2**256 - 2**32 * 351 + 1
 M = 1 << 256
@@ -421,34 +422,13 @@ def case_set(op, part):
 # ---- the harness ---------------------------------------------------------------------------------------------------------------
 def build_harness(exe, defines=(), csrc=None):
     """hipcc for gfx950 with the library's flags (-O3, the inline asm on) plus `defines`"""
-    csrc = csrc or os.path.join(ROOT, "starks_amd", "csrc")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-I", csrc] + ["-D" + d for d in defines]
-    subprocess.check_call(cmd + [HARNESS, "-o", str(exe)], timeout=600)
-    return str(exe)
+    return native_harness.build(HARNESS, exe, defines, csrc)
 
 
 def run_jobs(exe, mode, jobs, workdir, timeout=600):
     """jobs: (op, part, grid, block, tag) -> {tag: result bytes}.  One process runs every job."""
-    lines, outs = [], {}
-    for op, part, grid, block, tag in jobs:
-        cases, data, _ = case_set(op, part)
-        inp = os.path.join(str(workdir), "%s.%s.in" % (op, part))
-        if not os.path.exists(inp):
-            with open(inp, "wb") as fh:
-                fh.write(data)
-        out = os.path.join(str(workdir), "%s.out" % tag)
-        lines.append("%s %d %d %d %s %s" % (op, len(cases), grid, block, inp, out))
-        outs[tag] = out
-    jf = os.path.join(str(workdir), "jobs.%s" % mode)
-    with open(jf, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
-    p = subprocess.run([exe, "--" + mode, jf], capture_output=True, text=True, timeout=timeout)
-    assert p.returncode == 0, "fp256_ops --%s exited %d: %s%s" % (mode, p.returncode, p.stdout, p.stderr)
-    res = {}
-    for tag, out in outs.items():
-        with open(out, "rb") as fh:
-            res[tag] = fh.read()
-    return res
+    return native_harness.run_jobs(exe, mode, jobs, workdir, lambda op, part: (len(case_set(op, part)[0]), case_set(op, part)[1]),
+                                   timeout)
 
 
 def mismatches(op, part, got, block=64, limit=5):
