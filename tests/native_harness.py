@@ -9,9 +9,10 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 
 def build(src, exe, defines=(), csrc=None, timeout=600):
-    """hipcc for gfx950 with the library's flags (-O3, the inline asm on) plus `defines`"""
+    """hipcc for gfx950 with the library's flags (-O3, the inline asm on) plus `defines`; `src` is one source or a list of them"""
     cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-I", csrc or CSRC] + ["-D" + d for d in defines]
-    subprocess.check_call(cmd + [src, "-o", str(exe)], timeout=timeout)
+    srcs = [src] if isinstance(src, str) else list(src)
+    subprocess.check_call(cmd + srcs + ["-o", str(exe)], timeout=timeout)
     return str(exe)
 
 
