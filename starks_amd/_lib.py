@@ -116,6 +116,8 @@ def lib():
         "sh_zpoly": (i32, [c_p, u8p, u64, c_p]),
         "sh_dev_lagrange_interp": (i32, [c_p, c_p, c_p, u64, c_p]),
         "sh_lagrange_interp": (i32, [c_p, u8p, u8p, u64, c_p]),
+        "sh_dev_poly_eval": (i32, [c_p, c_p, u64, u32, c_p, u64, c_p]),
+        "sh_poly_eval": (i32, [c_p, u8p, u64, u32, u8p, u64, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares

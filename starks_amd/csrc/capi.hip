@@ -1849,6 +1849,18 @@ struct DevOps {
     return SH_OK;
   }
   int sub(const fp* a, const fp* b, fp* out, uint64_t n) { HIP_TRY(c, shk_pa_sub(a, b, out, n, c->stream)); return SH_OK; }
+  int eval_pow_table(const fp* xs, uint64_t m, uint32_t lgS, fp* tbl) { HIP_TRY(c, shk_pe_pow_table(xs, m, lgS, tbl, c->stream)); return SH_OK; }
+  int eval_direct(const PeDirect& s, const fp* coefs, const fp* tbl, fp* dst) { HIP_TRY(c, shk_pe_direct(s, coefs, tbl, dst, c->stream)); return SH_OK; }
+  int eval_sum(const PeDirect& s, const fp* part, fp* out) { HIP_TRY(c, shk_pe_sum(s, part, out, c->stream)); return SH_OK; }
+  int eval_chunks(const fp* coefs, uint64_t n, uint64_t batch, uint64_t N, uint64_t C, fp* dst) {
+    HIP_TRY(c, shk_pe_chunks(coefs, n, batch, N, C, dst, c->stream));
+    return SH_OK;
+  }
+  int bcast_mul(fp* a, const fp* b, uint64_t rows, uint64_t len) { HIP_TRY(c, shk_pe_bcast_mul(a, b, rows, len, c->stream)); return SH_OK; }
+  int eval_combine(const fp* leaves, const fp* xs, uint64_t m, uint64_t N, uint64_t C, uint64_t batch, fp* out) {
+    HIP_TRY(c, shk_pe_combine(leaves, xs, m, N, C, batch, out, c->stream));
+    return SH_OK;
+  }
   int buf(int slot, uint64_t elems, fp** out) { return ws(sh_ctx::WS_PA_TREE + slot, elems, out); }
   int ws(int slot, uint64_t elems, fp** out) {
     void* p = nullptr;
@@ -1865,6 +1877,20 @@ int pa_lc_nonzero(sh_ctx* c, const void* d_b, uint64_t nb, bool* nonzero) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   *nonzero = !fp_eq_canon(fp_canon(lc), fp_zero());
   return SH_OK;
+}
+
+// sh_poly_eval's limits and checks (include/starkhip.h), then the path: STARKHIP_EVAL_PATH, else poly_items.cuh's cost rule
+constexpr uint64_t PE_MAX_COEFS = 1ull << 25, PE_MAX_TOTAL = 1ull << 26, PE_MAX_POINTS = 1ull << 20;
+int pe_check(sh_ctx* c, const void* coefs, uint64_t n, uint32_t batch, const void* xs, uint64_t m, const void* out) {
+  if (!c || batch == 0 || (n && !coefs) || (m && (!xs || !out))) return SH_ERR_INVALID;
+  if (n > PE_MAX_COEFS || (uint64_t)batch * n > PE_MAX_TOTAL || m > PE_MAX_POINTS) return SH_ERR_UNSUPPORTED;
+  const uint64_t out_bytes = 32ull * batch * m;
+  if (any_overlap(out, out_bytes, coefs, 32ull * batch * n) || any_overlap(out, out_bytes, xs, 32 * m)) return SH_ERR_INVALID;
+  return SH_OK;
+}
+bool pe_direct(uint64_t n, uint64_t m, uint32_t batch) {
+  const int forced = shk_knobs().eval_path;
+  return forced ? forced == 1 : pe_direct_preferred(n, m, batch);
 }
 }  // namespace
 
@@ -1979,6 +2005,28 @@ int sh_lagrange_interp(sh_ctx* c, const uint8_t* xs, const uint8_t* ys, uint64_t
   SH_TRY(o.ws(sh_ctx::WS_MISC, n, &d_out));
   SH_TRY(pa_lagrange(o, x, y, n, d_out));
   return download_wire(c, d_out, out, n);
+}
+
+int sh_dev_poly_eval(sh_ctx* c, const void* d_coefs, uint64_t n, uint32_t batch, const void* d_xs, uint64_t m, void* d_out) {
+  SH_TRY(pe_check(c, d_coefs, n, batch, d_xs, m, d_out));
+  if (m == 0) return SH_OK;
+  SH_TRY(enter(c));
+  DevOps o{c};
+  return pa_eval(o, static_cast<const fp*>(d_coefs), n, batch, static_cast<const fp*>(d_xs), m, static_cast<fp*>(d_out),
+                 pe_direct(n, m, batch));
+}
+
+int sh_poly_eval(sh_ctx* c, const uint8_t* coefs, uint64_t n, uint32_t batch, const uint8_t* xs, uint64_t m, uint8_t* out) {
+  SH_TRY(pe_check(c, coefs, n, batch, xs, m, out));
+  if (m == 0) return SH_OK;
+  SH_TRY(enter(c));
+  DevOps o{c};
+  fp *x = nullptr, *d_xs, *d_out;
+  if (n) SH_TRY(upload_padded(c, coefs, n, n, batch, sh_ctx::WS_X, &x));
+  SH_TRY(upload_padded(c, xs, m, m, 1, sh_ctx::WS_Y, &d_xs));
+  SH_TRY(o.ws(sh_ctx::WS_MISC, (uint64_t)batch * m, &d_out));
+  SH_TRY(pa_eval(o, x, n, batch, d_xs, m, d_out, pe_direct(n, m, batch)));
+  return download_wire(c, d_out, out, (uint64_t)batch * m);
 }
 
 }  // extern "C"

@@ -190,3 +190,17 @@ hipError_t shk_pa_inv1(const fp* src, fp* dst, hipStream_t st);
 hipError_t shk_pa_deriv_rev(const fp* top, fp* out, uint64_t N, uint64_t n, hipStream_t st);
 hipError_t shk_pa_weights(const fp* ys, const fp* inv, fp* out, uint64_t n, uint64_t N, hipStream_t st);
 hipError_t shk_pa_sub(const fp* a, const fp* b, fp* out, uint64_t n, hipStream_t st);
+
+// ---- poly_eval.hip: evaluation at arbitrary points (polynomial.py:158-164; poly_items.cuh: pa_eval_direct, pa_eval_tree) ----------
+// tbl[b m + i] = x_i^(2^b), b <= lgS
+hipError_t shk_pe_pow_table(const fp* xs, uint64_t m, uint32_t lgS, fp* tbl, hipStream_t st);
+// dst[b][w][i]: workgroup w's sum for point i of polynomial b (canonical when s.W = 1); coefs [batch][n]
+hipError_t shk_pe_direct(const PeDirect& s, const fp* coefs, const fp* tbl, fp* dst, hipStream_t st);
+// out[b][i] = the canonical sum of part[b][0, W)[i]
+hipError_t shk_pe_sum(const PeDirect& s, const fp* part, fp* out, hipStream_t st);
+// dst [batch C][N] = the reversed chunks of coefs [batch][n] (pe_chunk_rev_item)
+hipError_t shk_pe_chunks(const fp* coefs, uint64_t n, uint64_t batch, uint64_t N, uint64_t C, fp* dst, hipStream_t st);
+// a[r][i] *= b[i], r < rows, i < len
+hipError_t shk_pe_bcast_mul(fp* a, const fp* b, uint64_t rows, uint64_t len, hipStream_t st);
+// out[b][i] = sum_j leaves[b C + j][i] (x_i^N)^j, canonical
+hipError_t shk_pe_combine(const fp* leaves, const fp* xs, uint64_t m, uint64_t N, uint64_t C, uint64_t batch, fp* out, hipStream_t st);

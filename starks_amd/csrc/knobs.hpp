@@ -18,12 +18,14 @@
 //                                  (ntt_narrow_pass_kernel; default 256 = the CUs of the chip; 0 = never)
 //   STARKHIP_WITNESS_GROUP=1|2|4|8|16  lanes per unit of the witness generator (witness.hip; default: chosen from the term table)
 //   STARKHIP_WITNESS_SLICE=k       steps per witness dispatch (default: about 2^13 sequential products per dispatch, at least 1)
+//   STARKHIP_EVAL_PATH=direct|tree  the path of every sh_poly_eval call (default: chosen per call, poly_items.cuh:pe_direct_preferred)
 // All of them exist for the parity tests over alternate plans (tests/test_gpu_parity.py::test_alternate_ntt_plans_parity,
 // tools/stress_plans.py) and for A/B measurements; the defaults are the measured best.
 #pragma once
 #include <stdlib.h>
 
 #include <mutex>
+#include <string>
 
 struct ShkKnobs {
   int tile_log = 10;         // passes of radix <= 2^8
@@ -39,6 +41,7 @@ struct ShkKnobs {
   long narrow_tiles = 256;   // 0: the narrow form is never used
   int witness_group = 0;     // 0: not given
   long witness_slice = 0;    // 0: not given
+  int eval_path = 0;         // 0: chosen per call, 1: direct, 2: tree
 };
 
 namespace shk_knobs_detail {
@@ -86,6 +89,10 @@ inline void parse(ShkKnobs* k) {
   if (const char* e = getenv("STARKHIP_WITNESS_SLICE")) {
     const long v = atol(e);
     if (v > 0) k->witness_slice = v;
+  }
+  if (const char* e = getenv("STARKHIP_EVAL_PATH")) {
+    const std::string v(e);
+    k->eval_path = v == "direct" ? 1 : v == "tree" ? 2 : 0;
   }
   if (const char* e = getenv("STARKHIP_NTT_RADICES")) {
     int r[4] = {0, 0, 0, 0}, cnt = 0, sum = 0;

@@ -1,6 +1,7 @@
-// poly_items.cuh -- the per-element and per-node steps of univariate polynomial arithmetic on the device (poly_arith.hip, driven
-// from capi.hip): exact products, division with remainder, zpoly and lagrange_interp (starks/polynomial.py:116-150,
-// starks/poly_utils.py:322-369), all built from batched cyclic NTTs of power-of-two sizes.
+// poly_items.cuh -- the per-element and per-node steps of univariate polynomial arithmetic on the device (poly_arith.hip and
+// poly_eval.hip, driven from capi.hip): exact products, division with remainder, zpoly and lagrange_interp (starks/polynomial.py:
+// 116-150, starks/poly_utils.py:322-369), all built from batched cyclic NTTs of power-of-two sizes, and evaluation at arbitrary
+// points (polynomial.py:158-164; at the end of this file).
 //
 // Product tree.  n points are padded with zeros to N = 2^lg points (a zero point adds a factor X, which the callers shift out
 // again).  A node of degree d is monic and stored as its d lower coefficients a, the leading 1 implicit.  Two siblings multiply
@@ -13,7 +14,7 @@
 // Numerators.  N_v = N_L Z_R + N_R Z_L with deg N < d: in the same size-2d transform N_L (X^d + b) is N_L (B + (-1)^i)
 // (pa_num_node).  At the leaves N = w_i, at the top N = sum_i w_i prod_{j != i} (X - x_j).
 //
-// Multipoint evaluation (Bernstein's scaled remainder tree).  For P with deg P < N and Z = prod (X - x_i), the fractional part
+// Multipoint evaluation (Bernstein's scaled remainder tree; used by lagrange_interp and, batched over chunks, by pa_eval_tree).  For P with deg P < N and Z = prod (X - x_i), the fractional part
 // of P / Z_v at a node v is y D_v(y), y = 1/X, where D_v holds |v| coefficients.  At the root D = rev_{N-1}(P) rev(Z)^-1 mod y^N
 // (one Newton inverse); a child c with sibling s takes D_c[k] = (D_v rev(Z_s))[d + k], k < d, the middle of a product that a
 // size-2d cyclic convolution leaves intact (pa_mid); at a leaf D = P(x_i).  rev(Z_s) = 1 + a_{d-1} y + ... + a_0 y^d
@@ -214,6 +215,36 @@ int pa_zpoly(Ops& o, const fp* xs, uint64_t n, fp* out) {
   return pa_cp(o, pa_level(tree, N, pa_log2(N), false), out, 1, n + 1, 0, 0, N, (int64_t)(N - n), 1, PA_ONE_AT_END | PA_CANON);
 }
 
+// The descent of the scaled remainder tree for `rows` polynomials over one tree of N points (kept levels): d0 holds the root's
+// [rows][N] coefficients D (above), d1 as much scratch; *leaves gets whichever of the two ends up holding [rows][N] leaf values, the
+// polynomials at x_0 .. x_{N-1}.  Every level is one batched forward transform of the parents, one of the children's rev(Z_c), the
+// middle-product launch and one batched inverse transform.  Scratch: t1 rows N, t2 2N, hat 2 rows N elements; for rows > 1 also zt
+// (2N), from which the children's transforms are copied to every row (for one row they are made in hat directly).
+template <class Ops>
+int pa_descend(Ops& o, fp* tree, uint64_t N, uint64_t rows, fp* d0, fp* d1, fp* t1, fp* t2, fp* hat, fp* zt, fp** leaves) {
+  fp *dcur = d0, *dnext = d1;
+  for (int j = (int)pa_log2(N) - 1; j >= 0; --j) {
+    const uint64_t d = 1ull << j, children = N >> j;
+    PA_TRY(o.ntt(dcur, t1, rows * children / 2, 2 * d, 0, false));
+    // rev(Z_c) = 1 + a_{d-1} y + ... + a_0 y^d of every child
+    PA_TRY(pa_cp(o, pa_level(tree, N, (uint32_t)j, true), t2, children, d + 1, d, d + 1, d, (int64_t)d, -1, PA_ONE_AT_END));
+    if (rows == 1) {
+      PA_TRY(o.ntt(t2, hat, children, 2 * d, d + 1, false));
+    } else {
+      PA_TRY(o.ntt(t2, zt, children, 2 * d, d + 1, false));
+      PA_TRY(pa_cp(o, zt, hat, rows, 2 * N, 0, 2 * N, 2 * N, 0, 1, 0));
+    }
+    PA_TRY(o.mid(t1, hat, (uint32_t)j + 1, rows * children));
+    PA_TRY(o.ntt(hat, hat, rows * children, 2 * d, 0, true));
+    PA_TRY(pa_cp(o, hat, dnext, rows * children, d, 2 * d, d, 2 * d, (int64_t)d, 1, 0));  // the middle: coefficients [d, 2d)
+    fp* t = dcur;
+    dcur = dnext;
+    dnext = t;
+  }
+  *leaves = dcur;
+  return 0;
+}
+
 // out[0, n) = sum_i y_i w_i prod_{j != i} (X - x_j), w_i = 1 / Z'(x_i), or 1 where Z'(x_i) = 0 (poly_utils.py:337-369); n >= 1
 template <class Ops>
 int pa_lagrange(Ops& o, const fp* xs, const fp* ys, uint64_t n, fp* out) {
@@ -234,20 +265,8 @@ int pa_lagrange(Ops& o, const fp* xs, const fp* ys, uint64_t n, fp* out) {
   PA_TRY(o.deriv_rev(top, R[1], N, n));
   PA_TRY(pa_mul(o, R[1], N, R[0], N, hat, t1, t2));  // 2N - 1 coefficients, the low N are D
   PA_TRY(pa_cp(o, hat, R[2], 1, N, 0, 0, N, 0, 1, 0));
-  fp *dcur = R[2], *dnext = R[3];
-  for (int j = (int)lg - 1; j >= 0; --j) {
-    const uint64_t d = 1ull << j, children = N >> j;
-    PA_TRY(o.ntt(dcur, t1, children / 2, 2 * d, 0, false));
-    // rev(Z_c) = 1 + a_{d-1} y + ... + a_0 y^d of every child
-    PA_TRY(pa_cp(o, pa_level(tree, N, (uint32_t)j, true), t2, children, d + 1, d, d + 1, d, (int64_t)d, -1, PA_ONE_AT_END));
-    PA_TRY(o.ntt(t2, hat, children, 2 * d, d + 1, false));
-    PA_TRY(o.mid(t1, hat, (uint32_t)j + 1, children));
-    PA_TRY(o.ntt(hat, hat, children, 2 * d, 0, true));
-    PA_TRY(pa_cp(o, hat, dnext, children, d, 2 * d, d, 2 * d, (int64_t)d, 1, 0));  // the middle: coefficients [d, 2d)
-    fp* t = dcur;
-    dcur = dnext;
-    dnext = t;
-  }
+  fp* dcur = nullptr;
+  PA_TRY(pa_descend(o, tree, N, 1, R[2], R[3], t1, t2, hat, nullptr, &dcur));
   // dcur[i] = Z'(x_i) = prod_{j != i} (x_i - x_j); the weights y_i / Z'(x_i) are the leaves of the numerator tree
   PA_TRY(o.multi_inv(dcur, t1, n));
   PA_TRY(o.weights(ys, t1, R[0], n, N));
@@ -264,4 +283,169 @@ int pa_lagrange(Ops& o, const fp* xs, const fp* ys, uint64_t n, fp* out) {
   }
   // the padded numerator is X^(N - n) times the true one
   return pa_cp(o, ncur, out, 1, n, 0, 0, N, (int64_t)(N - n), 1, PA_CANON);
+}
+
+// ---- evaluation at arbitrary points: out[b][i] = P_b(x_i) (polynomial.py:158-164) ---------------------------------------------------
+FP_HD void pa_st(fp* p, const fp& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  fp_store(p, v);
+#else
+  *p = v;
+#endif
+}
+
+// Direct path (poly_eval.hip).  The S = W * PE_WG lanes of a point group split the coefficients by residue: lane g runs Horner in
+// y = x^S over c[g], c[g + S], c[g + 2S], ... for each of the group's G points (held in registers: every coefficient load feeds G
+// independent products), then multiplies by x^g, one product per set bit of g from a per-point table of x^(2^b).  The lanes' sums
+// are added across the workgroup and, when W > 1, across workgroups by a second launch: modular addition is exact, so neither the
+// grid shape nor the order changes a bit of the result.  About batch n m products; the coefficients are read once per point group.
+constexpr uint32_t PE_WG = 256;           // lanes per workgroup
+constexpr uint32_t PE_GROUP = 4;          // points per lane when m >= 4 (else 1)
+constexpr uint64_t PE_MIN_T = 64;         // W doubles only while every lane keeps at least this many coefficients
+constexpr uint64_t PE_TARGET_WGS = 2048;  // ... and the grid is below this many workgroups (8 per CU)
+struct PeDirect {
+  uint64_t n, m, batch;
+  uint64_t W;       // workgroups per point group; S = W PE_WG lanes share the group's coefficients
+  uint64_t T;       // coefficients per lane, ceil(n / S)
+  uint64_t groups;  // point groups, ceil(m / G)
+  uint32_t lgS, G;
+};
+inline PeDirect pe_direct_shape(uint64_t n, uint64_t m, uint64_t batch) {
+  PeDirect s{n, m, batch, 1, 0, 0, 0, m >= PE_GROUP ? PE_GROUP : 1u};
+  s.groups = (m + s.G - 1) / s.G;
+  while (2 * s.W * PE_WG * PE_MIN_T <= n && s.W * s.groups * batch < PE_TARGET_WGS) s.W *= 2;
+  s.lgS = pa_log2(s.W * PE_WG);
+  s.T = (n + (s.W << 8) - 1) / (s.W << 8);
+  return s;
+}
+
+// tbl[b m + i] = x_i^(2^b), b <= lgS (y = x^S is entry lgS)
+FP_HD void pe_pow_table_item(const fp* xs, uint64_t m, uint32_t lgS, fp* tbl, uint64_t i) {
+  fp v = pa_ld(xs + i);
+  for (uint32_t b = 0;; ++b) {
+    pa_st(tbl + b * m + i, v);
+    if (b == lgS) break;
+    v = fp_sqr(v);
+  }
+}
+
+// lane g of the group of points i0 .. i0 + G - 1 for the n coefficients c: acc[q] = x_q^g sum_t c[g + S t] x_q^(S t), lazily reduced
+// (zero for a point at or beyond m)
+template <int G>
+FP_HD void pe_lane(const PeDirect& s, const fp* c, const fp* tbl, uint64_t i0, uint64_t g, fp acc[G]) {
+  fp y[G];
+#pragma unroll
+  for (int q = 0; q < G; ++q) {
+    y[q] = i0 + q < s.m ? pa_ld(tbl + (uint64_t)s.lgS * s.m + i0 + q) : fp_zero();
+    acc[q] = fp_zero();
+  }
+  for (uint64_t t = s.T; t-- > 0;) {
+    const uint64_t k = g + (t << s.lgS);
+    const fp v = k < s.n ? pa_ld(c + k) : fp_zero();
+#pragma unroll
+    for (int q = 0; q < G; ++q) acc[q] = fp_add(fp_mul(acc[q], y[q]), v);
+  }
+  for (uint32_t b = 0; b < s.lgS; ++b)
+    if ((g >> b) & 1) {
+#pragma unroll
+      for (int q = 0; q < G; ++q)
+        if (i0 + q < s.m) acc[q] = fp_mul(acc[q], pa_ld(tbl + (uint64_t)b * s.m + i0 + q));
+    }
+}
+
+// out[b][i] from the W workgroup sums part[b][w][i], canonical
+FP_HD fp pe_sum_item(const PeDirect& s, const fp* part, uint64_t b, uint64_t i) {
+  fp acc = fp_zero();
+  for (uint64_t w = 0; w < s.W; ++w) acc = fp_add(acc, pa_ld(part + (b * s.W + w) * s.m + i));
+  return fp_canon(acc);
+}
+
+// Tree path.  Over the product tree of the points padded with zeros to N = 2^ceil(log2 m) (at least 2), each polynomial is split into
+// C = ceil(n / N) chunks of N coefficients, P = sum_j P_j X^(jN).  One Newton inverse of rev(Z) serves every chunk: the root step
+// D = rev_{N-1}(P_j) rev(Z)^-1 mod y^N is one batched product over all batch C rows, one batched descent (pa_descend) gives every
+// P_j(x_i), and pe_combine_item adds the chunks by Horner in x_i^N.  Dividing P by Z instead (pa_divmod) would need a Newton inverse
+// as long as P.
+// row r = b C + j: rev_{N-1}(P_{b,j})[k] = coefs[b][j N + N - 1 - k], 0 beyond n
+FP_HD fp pe_chunk_rev_item(const fp* coefs, uint64_t n, uint64_t N, uint64_t C, uint64_t r, uint64_t k) {
+  const uint64_t b = r / C, s = (r - b * C) * N + N - 1 - k;
+  return s < n ? pa_ld(coefs + b * n + s) : fp_zero();
+}
+
+// out[b][i] = sum_j P_{b,j}(x_i) (x_i^N)^j, canonical; leaves: [batch C][N]
+FP_HD fp pe_combine_item(const fp* leaves, const fp* xs, uint64_t N, uint64_t C, uint64_t b, uint64_t i) {
+  fp xN = fp_zero();
+  if (C > 1) {
+    xN = pa_ld(xs + i);
+    for (uint64_t e = 1; e < N; e <<= 1) xN = fp_sqr(xN);
+  }
+  fp acc = fp_zero();
+  for (uint64_t j = C; j-- > 0;) acc = fp_add(fp_mul(acc, xN), pa_ld(leaves + (b * C + j) * N + i));
+  return fp_canon(acc);
+}
+
+// Path choice: the direct path costs about batch n m products at 1.9e5 per us plus a 50 us floor; the tree about 150 us of launches
+// per level, its batched transforms (N lg^2 elements for the tree and the inverse, 3 R N lg for the R = batch C rows' root step and
+// descent, at 8e4 elements per us) and 0.8 us per row (the batched transforms of many short rows).  The constants are fitted to the
+// MI355X times of both forced paths over twelve shapes (profiles/r10_poly_eval.json, crossover_ms), which put the crossover near
+// n m = 2^29 for n = m / 4 .. 8 m: (2^15, 2^13) direct, (2^16, 2^13) tree.
+constexpr double PE_DIRECT_PRODUCTS_PER_US = 1.9e5;
+constexpr double PE_DIRECT_FLOOR_US = 50.0;
+constexpr double PE_TREE_US_PER_LEVEL = 150.0;
+constexpr double PE_TREE_ELEMENTS_PER_US = 8.0e4;
+constexpr double PE_TREE_US_PER_ROW = 0.8;
+inline bool pe_direct_preferred(uint64_t n, uint64_t m, uint64_t batch) {
+  const uint64_t N = pa_pow2_at_least(m), C = (n + N - 1) / N;
+  const double lg = (double)pa_log2(N), R = (double)batch * (double)C;
+  const double direct = PE_DIRECT_FLOOR_US + (double)batch * (double)n * (double)m / PE_DIRECT_PRODUCTS_PER_US;
+  const double tree = PE_TREE_US_PER_LEVEL * lg + ((double)N * lg * lg + 3.0 * R * (double)N * lg) / PE_TREE_ELEMENTS_PER_US +
+                      PE_TREE_US_PER_ROW * R;
+  return direct <= tree;
+}
+
+// Ops (evaluation only): eval_pow_table(xs, m, lgS, tbl), eval_direct(PeDirect, coefs, tbl, dst) (dst[b][w][i]: the workgroup sums,
+//      canonical when W = 1), eval_sum(PeDirect, part, out), eval_chunks(coefs, n, batch, N, C, dst) ([batch C][N] rows of
+//      pe_chunk_rev_item), bcast_mul(a, b, rows, len) (a[r][i] *= b[i]), eval_combine(leaves, xs, m, N, C, batch, out)
+template <class Ops>
+int pa_eval_direct(Ops& o, const fp* coefs, uint64_t n, uint64_t batch, const fp* xs, uint64_t m, fp* out) {
+  const PeDirect s = pe_direct_shape(n, m, batch);
+  fp *tbl, *part = out;
+  PA_TRY(o.buf(PA_BUF_1, (s.lgS + 1) * m, &tbl));
+  if (s.W > 1) PA_TRY(o.buf(PA_BUF_2, batch * s.W * m, &part));
+  PA_TRY(o.eval_pow_table(xs, m, s.lgS, tbl));
+  PA_TRY(o.eval_direct(s, coefs, tbl, part));
+  return s.W > 1 ? o.eval_sum(s, part, out) : 0;
+}
+
+template <class Ops>
+int pa_eval_tree(Ops& o, const fp* coefs, uint64_t n, uint64_t batch, const fp* xs, uint64_t m, fp* out) {
+  const uint64_t N = pa_pow2_at_least(m), C = (n + N - 1) / N, R = batch * C;
+  const uint32_t lg = pa_log2(N);
+  fp *tree, *hat, *t1, *t2, *rows, *r;
+  PA_TRY(o.buf(PA_BUF_TREE, (lg + 1) * N, &tree));
+  PA_TRY(o.buf(PA_BUF_3, 2 * N, &hat));  // the tree's transforms, then the descent's zt
+  PA_TRY(o.buf(PA_BUF_1, R * N > 2 * N ? R * N : 2 * N, &t1));
+  PA_TRY(o.buf(PA_BUF_2, 2 * N, &t2));
+  PA_TRY(o.buf(PA_BUF_4, 2 * R * N, &rows));  // the rows' root products, then the descent's transforms
+  PA_TRY(o.buf(PA_BUF_5, 2 * N + 2 * R * N, &r));
+  fp *g = r, *rz = r + N, *d0 = r + 2 * N, *d1 = d0 + R * N;
+  PA_TRY(pa_tree_up(o, xs, m, N, tree, true, hat));
+  PA_TRY(pa_cp(o, pa_level(tree, N, lg, true), rz, 1, N, 0, 0, N, (int64_t)N, -1, PA_ONE_AT_END));  // rev(Z) mod y^N
+  PA_TRY(pa_inverse(o, rz, N, N, g, t1, t2));
+  PA_TRY(o.ntt(g, t2, 1, 2 * N, N, false));
+  PA_TRY(o.eval_chunks(coefs, n, batch, N, C, d0));
+  PA_TRY(o.ntt(d0, rows, R, 2 * N, N, false));
+  PA_TRY(o.bcast_mul(rows, t2, R, 2 * N));
+  PA_TRY(o.ntt(rows, rows, R, 2 * N, 0, true));
+  PA_TRY(pa_cp(o, rows, d0, R, N, 2 * N, N, 2 * N, 0, 1, 0));  // D: the low N coefficients of each row
+  fp* leaves = nullptr;
+  PA_TRY(pa_descend(o, tree, N, R, d0, d1, t1, t2, rows, hat, &leaves));
+  return o.eval_combine(leaves, xs, m, N, C, batch, out);
+}
+
+// out[b][i] = sum_k coefs[b][k] x_i^k, canonical, for b < batch, i < m (n = 0: zeros)
+template <class Ops>
+int pa_eval(Ops& o, const fp* coefs, uint64_t n, uint64_t batch, const fp* xs, uint64_t m, fp* out, bool direct) {
+  if (m == 0) return 0;
+  if (n == 0) return pa_cp(o, nullptr, out, 1, batch * m, 0, 0, 0, 0, 1, 0);
+  return direct ? pa_eval_direct(o, coefs, n, batch, xs, m, out) : pa_eval_tree(o, coefs, n, batch, xs, m, out);
 }

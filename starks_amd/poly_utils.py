@@ -5,10 +5,11 @@
     multi_interp_4(field, xsets, ysets) -> [Poly]      (the cubic through each row's four points)
     zpoly(field, roots) -> Poly                        (prod (X - x_i): a product tree of batched NTTs, O(n log^2 n))
     lagrange_interp(field, xs, ys) -> Poly             (the reference's interpolant, O(n log^2 n) instead of its O(n^3))
+    multi_eval(field, poly, xs) -> sequence          (poly(x) at every point: direct Horner lanes or a remainder tree)
     multi_inv_wire(data) -> bytes, multi_interp_4_wire(xs, ys, rows) -> bytes,
     zpoly_wire(xs) -> bytes, lagrange_interp_wire(xs, ys) -> bytes   (wire form in and out, for large inputs)
 
-For the MiMC prime both always run on the GPU through libstarkhip.so (sh_multi_inv, sh_multi_interp_4) and raise when the library
+For the MiMC prime they always run on the GPU through libstarkhip.so (sh_multi_inv, sh_multi_interp_4) and raise when the library
 or the device is missing: there is no CPU fallback for them.  Another modulus (the reference's own tests use Z/7) is outside the hot
 path: there the reference's algorithm runs on the host on the field's own elements, as fft._host_dft does for transforms.
 
@@ -138,6 +139,18 @@ def lagrange_interp(field, xs, ys):
     if not _on_device(field):
         return _host_lagrange_interp(field, xs, ys)
     return polys_over(WireList(lagrange_interp_wire(_lib.to_wire(xs), _lib.to_wire(ys)), field))
+
+
+def multi_eval(field, poly, xs):
+    """Polynomial.__call__ (polynomial.py:158-164) at every x of xs: for the MiMC field one sh_poly_eval call, a WireList of the
+    field's elements (raises without a device, like multi_inv); for any other ring poly(x) per point on the host, a list.  poly is a
+    Polynomial or a sequence of coefficients (constant first)."""
+    coefficients = poly.coefficients if hasattr(poly, "coefficients") else list(poly)
+    if not _on_device(field):
+        p = poly if callable(poly) else polynomials_over(field)(coefficients)
+        return [p(x) for x in xs]
+    from .polynomial import eval_wire
+    return WireList(eval_wire(_lib.to_wire(coefficients), _lib.to_wire(list(xs))), field)
 
 
 # ---- host forms for other moduli (never the MiMC field) ---------------------------------------------------------------------------
