@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "fp256.cuh"
+#include "knobs.hpp"
 
 struct NttPassArgs {
   const fp* src;
@@ -32,8 +33,12 @@ struct NttPassArgs {
 };
 
 // ---- ntt.hip ----------------------------------------------------------------------------------
-// Launch one tile pass (radix 2^log_R).  Returns hipSuccess or the launch error.
+// Launch one tile pass (radix 2^log_R) in the cell shk_ntt_choose_cell (knobs.hpp) picks under the knobs of the process.  Returns
+// hipSuccess or the launch error.
 hipError_t shk_launch_ntt_pass(int log_R, bool last, const NttPassArgs& a, hipStream_t st);
+// The same pass in one named kernel instantiation (tests/native/ntt_ops.hip runs each on its own); hipErrorInvalidValue for a cell
+// that does not exist (knobs.hpp: shk_ntt_cell_exists).  The caller answers for the arguments: nothing here checks them.
+hipError_t shk_launch_ntt_cell(const ShkNttCell& cell, int log_R, bool last, const NttPassArgs& a, hipStream_t st);
 hipError_t shk_launch_ntt_tiny(const fp* src, fp* dst, uint32_t n, uint32_t batch, const fp* scale, hipStream_t st);
 
 // ---- kernels.hip: conversions, powers, Merkle, FRI fold, sampling, branch gather ------------------

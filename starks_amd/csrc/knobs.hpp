@@ -125,6 +125,71 @@ inline const ShkKnobs& shk_knobs() {
   return knobs;
 }
 
+// ---- which kernel a pass runs in ("cell") ------------------------------------------------------------------------------------------
+// One instantiation of the pass kernels of ntt_kernels.cuh is named by (form, tile_log, log_R, LAST): ntt_pass_kernel<log_R,
+// tile_log - log_R, LAST> (SHK_NTT_TILE) or ntt_narrow_pass_kernel<log_R, tile_log - log_R, LAST> (SHK_NTT_NARROW).  xcd: the launch
+// maps adjacent tiles to the same XCD (tile form only; a property of the launch, not of the instantiation).
+enum { SHK_NTT_NONE = -1, SHK_NTT_TILE = 0, SHK_NTT_NARROW = 1 };
+struct ShkNttCell {
+  int form;
+  int tile_log;
+  bool xcd;
+};
+// what the choice depends on, out of NttPassArgs (internal.hpp)
+struct ShkNttPassShape {
+  unsigned long long total;  // columns or rows of the launch
+  unsigned log_n, log_S, pass_index;
+};
+// narrow passes of at most this many 1024-element tiles run as 512-element tiles of 256 threads (radix <= 2^8)
+#ifndef SHK_NARROW_HALF_TILES
+#define SHK_NARROW_HALF_TILES 128
+#endif
+
+// The instantiations that exist; ntt.hip compiles exactly these (shk_launch_ntt_cell).  Tile form: 2048-element tiles for every
+// radix, 1024 up to radix 2^10, 512 up to 2^8 (a thread holds four elements of at least one row: log_R <= tile_log), 4096 from
+// radix 2^4 (STARKHIP_TILE_LOGS = 12 has always been ignored below that; the two kernels per LAST that used to be compiled for
+// radix 2^2 and 2^3 could not be launched).  Narrow form: 1024 elements up to radix 2^10, 512 up to 2^8.
+constexpr bool shk_ntt_cell_exists(int form, int tile_log, int log_R) {
+  if (log_R < 2 || log_R > 11) return false;
+  if (form == SHK_NTT_NARROW) return tile_log == 10 ? log_R <= 10 : tile_log == 9 && log_R <= 8;
+  if (form != SHK_NTT_TILE) return false;
+  return tile_log == 12 ? log_R >= 4 : tile_log == 11 ? true : tile_log == 10 ? log_R <= 10 : tile_log == 9 && log_R <= 8;
+}
+
+// The cell of one pass (radix 2^log_R, row pass when last) under the knobs kn.  form SHK_NTT_NONE: no such radix.
+//   narrow form: at most kn.narrow_tiles 1024-element tiles, radix <= 2^10, and no tile size forced for this pass (STARKHIP_TILE_LOGS);
+//       up to SHK_NARROW_HALF_TILES of them and radix <= 2^8: 512-element tiles -- the launch then has at most one wave per SIMD.
+//   else tile form.  Radix <= 2^8: the pass's STARKHIP_TILE_LOGS entry (4096 from radix 2^4 only, else it is ignored); else 2048 for
+//       the FIRST column pass of a long transform (P = 1, radix 2^8, n / R >= 2^16) unless STARKHIP_TILE_LOG is given: twice the
+//       columns per row are worth + 3.6 % on a 2^24-point transform (profiles/r03_first_pass_tile_2p24.txt), below that distance
+//       and at radix 2^7 the 1024-element tiles stay ahead; else STARKHIP_TILE_LOG (default 1024).
+//       Radix >= 2^9 (the two-pass plans of 2^17 .. 2^20 points): the pass's STARKHIP_TILE_LOGS entry when it is 10 .. 12 (1024 up to
+//       radix 2^10 only), else STARKHIP_TILE_LOG_BIG under the same limit (default 2048: 64 KiB, two workgroups per CU).
+//   xcd (ntt_kernels.cuh: shk_launch_tile_kernel): from 64 tiles up, when STARKHIP_XCD_SWZ is 2, or 1 and a tile has fewer than 4 columns.
+inline ShkNttCell shk_ntt_choose_cell(const ShkKnobs& kn, int log_R, bool last, const ShkNttPassShape& a) {
+  if (log_R < 2 || log_R > 11) return {SHK_NTT_NONE, 0, false};
+  const int f = a.pass_index < 8 ? kn.tile_logs[a.pass_index] : 0;
+  if (log_R <= 10) {
+    const int log_T = 10 - log_R;
+    const unsigned long long tiles = (a.total + ((1ull << log_T) - 1)) >> log_T;
+    if (kn.narrow_tiles > 0 && tiles != 0 && tiles <= (unsigned long long)kn.narrow_tiles && !f)
+      return {SHK_NTT_NARROW, (log_R <= 8 && tiles <= SHK_NARROW_HALF_TILES) ? 9 : 10, false};
+  }
+  int tl;
+  if (log_R <= 8) {
+    if ((f == 12 && log_R >= 4) || f == 11 || f == 10 || f == 9) tl = f;
+    else if (!last && log_R == 8 && a.log_S + 8 == a.log_n && a.log_S >= 16 && !kn.tile_forced) tl = 11;
+    else tl = kn.tile_log == 10 ? 10 : kn.tile_log == 9 ? 9 : 11;
+  } else {
+    if (f == 12 || f == 11 || (f == 10 && log_R <= 10)) tl = f;
+    else if (log_R <= 10 && kn.tile_log_big == 10) tl = 10;
+    else tl = kn.tile_log_big <= 11 ? 11 : 12;
+  }
+  const int log_t = tl - log_R;
+  const unsigned long long tiles = (a.total + ((1ull << log_t) - 1)) >> log_t;
+  return {SHK_NTT_TILE, tl, kn.xcd_swz && (kn.xcd_swz == 2 || log_t < 2) && tiles >= 64};
+}
+
 // The passes of a 2^log_n-point transform: log2 radices into out[0..4), returns their number.
 //   n <= 2^8: one pass.  2^9 .. 2^16: two passes of 1024-element tiles.  2^17 .. 2^20: two passes of radix 2^8 .. 2^10 over
 //   2048-element tiles -- (9, 8), (9, 9), (9, 10), (10, 10) -- measured ahead of three passes there (one inter-pass twiddle

@@ -6,113 +6,84 @@
 #include "knobs.hpp"
 #include "ntt_kernels.cuh"
 
-#ifndef SHK_NARROW_HALF_TILES
-#define SHK_NARROW_HALF_TILES 128
-#endif
-
 namespace {
 
 template <int LOG_R, bool LAST, int TILE_LOG>
-hipError_t launch_tile(const NttPassArgs& a, hipStream_t st) {
+hipError_t launch_tile(const NttPassArgs& a, bool xcd, hipStream_t st) {
   constexpr int LOG_T = TILE_LOG - LOG_R;
   static std::atomic<uint64_t> attr_done{0};
   return shk_launch_tile_kernel(ntt_pass_kernel<LOG_R, LOG_T, LAST>, attr_done, LOG_T, 1u << (TILE_LOG - 2), (size_t)32 << TILE_LOG,
-                                a, st);
+                                a, xcd, st);
 }
 
-// narrow launches (ntt_kernels.cuh): at most kn.narrow_tiles tiles of 1024 elements, radix <= 2^10
+// narrow launches (ntt_kernels.cuh): one butterfly per thread, 1024-element tiles of 512 threads or 512-element tiles of 256
+template <int LOG_R, bool LAST, int TILE_LOG>
+hipError_t launch_narrow(const NttPassArgs& a, hipStream_t st) {
+  constexpr int LOG_T = TILE_LOG - LOG_R;
+  const uint64_t tiles = (a.total + ((1ull << LOG_T) - 1)) >> LOG_T;
+  if (tiles == 0 || tiles > 0x7ffffff0ull) return hipErrorInvalidValue;  // the kernel clamps to column total - 1
+  hipLaunchKernelGGL((ntt_narrow_pass_kernel<LOG_R, LOG_T, LAST>), dim3((unsigned)tiles), dim3(1u << (TILE_LOG - 1)), 0, st, a);
+  return hipGetLastError();
+}
+
+// The one switch over the instantiations: exactly the cells of shk_ntt_cell_exists (knobs.hpp) are compiled.
 template <int LOG_R, bool LAST>
-bool launch_narrow(const NttPassArgs& a, hipStream_t st, hipError_t* err) {
-  if constexpr (LOG_R <= 10) {
-    const ShkKnobs& kn = shk_knobs();
-    constexpr int LOG_T = 10 - LOG_R;
-    const uint64_t tiles = (a.total + ((1ull << LOG_T) - 1)) >> LOG_T;
-    if (kn.narrow_tiles <= 0 || tiles == 0 || tiles > (uint64_t)kn.narrow_tiles) return false;
-    if (a.pass_index < 8 && kn.tile_logs[a.pass_index]) return false;  // a forced tile size means the tile-pass kernels
-    // Up to SHK_NARROW_HALF_TILES tiles: 512-element tiles, 256 threads -- the launch then has at most one wave per SIMD, and a level's
-    // product chain is not shared with a second wave of the same workgroup (radix <= 2^8: at least two columns / rows per tile)
-    if constexpr (LOG_R <= 8) {
-      if (tiles <= SHK_NARROW_HALF_TILES) {
-        constexpr int LOG_T9 = 9 - LOG_R;
-        const uint64_t tiles9 = (a.total + ((1ull << LOG_T9) - 1)) >> LOG_T9;
-        hipLaunchKernelGGL((ntt_narrow_pass_kernel<LOG_R, LOG_T9, LAST>), dim3((unsigned)tiles9), dim3(256), 0, st, a);
-        *err = hipGetLastError();
-        return true;
-      }
+hipError_t launch_cell(const ShkNttCell& c, const NttPassArgs& a, hipStream_t st) {
+  if (c.form == SHK_NTT_NARROW) {
+    if (c.xcd) return hipErrorInvalidValue;
+    if constexpr (shk_ntt_cell_exists(SHK_NTT_NARROW, 10, LOG_R)) {
+      if (c.tile_log == 10) return launch_narrow<LOG_R, LAST, 10>(a, st);
     }
-    hipLaunchKernelGGL((ntt_narrow_pass_kernel<LOG_R, LOG_T, LAST>), dim3((unsigned)tiles), dim3(1u << (LOG_R + LOG_T - 1)), 0, st, a);
-    *err = hipGetLastError();
-    return true;
-  }
-  return false;
-}
-
-// The FIRST column pass of a long transform (P = 1: the rows of a tile are n / R elements apart) gets 2048-element tiles once that
-// distance reaches 2 MiB (n / R >= 2^16): twice the columns per row (256-byte segments at radix 2^8) are worth + 3.6 % on a
-// 2^24-point transform and + 4 % on two of them (profiles/r03_first_pass_tile_2p24.txt); below that distance the 1024-element
-// tiles of the other passes stay ahead, and so they do for the radix-2^7 first pass of the four-pass plan of 2^25 points: the
-// rule is radix 2^8 only.  The knobs (knobs.hpp, read once per process) override it.
-template <int LOG_R, bool LAST>
-hipError_t launch(const NttPassArgs& a, hipStream_t st) {
-  const ShkKnobs& kn = shk_knobs();
-  hipError_t ne = hipSuccess;
-  if (launch_narrow<LOG_R, LAST>(a, st, &ne)) return ne;
-  if (const int f = a.pass_index < 8 ? kn.tile_logs[a.pass_index] : 0) {
-    if (f == 12 && LOG_R >= 4) return launch_tile<LOG_R, LAST, 12>(a, st);
-    if (f == 11) return launch_tile<LOG_R, LAST, 11>(a, st);
-    if (f == 10) return launch_tile<LOG_R, LAST, 10>(a, st);
-    if (f == 9) return launch_tile<LOG_R, LAST, 9>(a, st);
-  }
-  if constexpr (!LAST && LOG_R == 8) {
-    if (a.log_S + LOG_R == a.log_n && a.log_S >= 16 && !kn.tile_forced) return launch_tile<LOG_R, LAST, 11>(a, st);
-  }
-  if (kn.tile_log == 10) return launch_tile<LOG_R, LAST, 10>(a, st);
-  if (kn.tile_log == 9) return launch_tile<LOG_R, LAST, 9>(a, st);
-  return launch_tile<LOG_R, LAST, 11>(a, st);
-}
-
-// Radices above 2^8 (the two-pass plans of 2^17 .. 2^20 points): 2048-element tiles (64 KiB, two workgroups per CU); the knobs
-// select 1024- or 4096-element tiles (128 KiB, 1024 threads, one workgroup per CU) for experiments.
-template <int LOG_R, bool LAST>
-hipError_t launch_big(const NttPassArgs& a, hipStream_t st) {
-  const ShkKnobs& kn = shk_knobs();
-  hipError_t ne = hipSuccess;
-  if (launch_narrow<LOG_R, LAST>(a, st, &ne)) return ne;
-  if (const int f = a.pass_index < 8 ? kn.tile_logs[a.pass_index] : 0) {
-    if (f == 12) return launch_tile<LOG_R, LAST, 12>(a, st);
-    if (f == 11) return launch_tile<LOG_R, LAST, 11>(a, st);
-    if constexpr (LOG_R <= 10) {
-      if (f == 10) return launch_tile<LOG_R, LAST, 10>(a, st);
+    if constexpr (shk_ntt_cell_exists(SHK_NTT_NARROW, 9, LOG_R)) {
+      if (c.tile_log == 9) return launch_narrow<LOG_R, LAST, 9>(a, st);
     }
+    return hipErrorInvalidValue;
   }
-  if constexpr (LOG_R <= 10) {
-    if (kn.tile_log_big == 10) return launch_tile<LOG_R, LAST, 10>(a, st);
+  if constexpr (shk_ntt_cell_exists(SHK_NTT_TILE, 12, LOG_R)) {
+    if (c.tile_log == 12) return launch_tile<LOG_R, LAST, 12>(a, c.xcd, st);
   }
-  if (kn.tile_log_big <= 11) return launch_tile<LOG_R, LAST, 11>(a, st);
-  return launch_tile<LOG_R, LAST, 12>(a, st);
+  if constexpr (shk_ntt_cell_exists(SHK_NTT_TILE, 11, LOG_R)) {
+    if (c.tile_log == 11) return launch_tile<LOG_R, LAST, 11>(a, c.xcd, st);
+  }
+  if constexpr (shk_ntt_cell_exists(SHK_NTT_TILE, 10, LOG_R)) {
+    if (c.tile_log == 10) return launch_tile<LOG_R, LAST, 10>(a, c.xcd, st);
+  }
+  if constexpr (shk_ntt_cell_exists(SHK_NTT_TILE, 9, LOG_R)) {
+    if (c.tile_log == 9) return launch_tile<LOG_R, LAST, 9>(a, c.xcd, st);
+  }
+  return hipErrorInvalidValue;
 }
 
 template <bool LAST>
-hipError_t dispatch(int log_R, const NttPassArgs& a, hipStream_t st) {
+hipError_t dispatch(const ShkNttCell& c, int log_R, const NttPassArgs& a, hipStream_t st) {
   switch (log_R) {
-    case 2: return launch<2, LAST>(a, st);
-    case 3: return launch<3, LAST>(a, st);
-    case 4: return launch<4, LAST>(a, st);
-    case 5: return launch<5, LAST>(a, st);
-    case 6: return launch<6, LAST>(a, st);
-    case 7: return launch<7, LAST>(a, st);
-    case 8: return launch<8, LAST>(a, st);
-    case 9: return launch_big<9, LAST>(a, st);
-    case 10: return launch_big<10, LAST>(a, st);
-    case 11: return launch_big<11, LAST>(a, st);
+    case 2: return launch_cell<2, LAST>(c, a, st);
+    case 3: return launch_cell<3, LAST>(c, a, st);
+    case 4: return launch_cell<4, LAST>(c, a, st);
+    case 5: return launch_cell<5, LAST>(c, a, st);
+    case 6: return launch_cell<6, LAST>(c, a, st);
+    case 7: return launch_cell<7, LAST>(c, a, st);
+    case 8: return launch_cell<8, LAST>(c, a, st);
+    case 9: return launch_cell<9, LAST>(c, a, st);
+    case 10: return launch_cell<10, LAST>(c, a, st);
+    case 11: return launch_cell<11, LAST>(c, a, st);
     default: return hipErrorInvalidValue;
   }
 }
 
 }  // namespace
 
+hipError_t shk_launch_ntt_cell(const ShkNttCell& c, int log_R, bool last, const NttPassArgs& a, hipStream_t st) {
+  if (!shk_ntt_cell_exists(c.form, c.tile_log, log_R)) return hipErrorInvalidValue;
+  return last ? dispatch<true>(c, log_R, a, st) : dispatch<false>(c, log_R, a, st);
+}
+
+// the library's own choice (knobs.hpp: shk_ntt_choose_cell, under the knobs of the process), then that cell
 hipError_t shk_launch_ntt_pass(int log_R, bool last, const NttPassArgs& a, hipStream_t st) {
-  return last ? dispatch<true>(log_R, a, st) : dispatch<false>(log_R, a, st);
+  const ShkNttPassShape shape{a.total, a.log_n, a.log_S, a.pass_index};
+  const ShkNttCell c = shk_ntt_choose_cell(shk_knobs(), log_R, last, shape);
+  if (c.form == SHK_NTT_NONE) return hipErrorInvalidValue;
+  return shk_launch_ntt_cell(c, log_R, last, a, st);
 }
 
 hipError_t shk_launch_ntt_tiny(const fp* src, fp* dst, uint32_t n, uint32_t batch, const fp* scale, hipStream_t st) {

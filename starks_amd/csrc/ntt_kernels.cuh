@@ -519,12 +519,12 @@ __global__ void __launch_bounds__(1 << (LOG_R + LOG_T - 1)) ntt_narrow_pass_kern
 // are dealt to the 8 XCDs round-robin, so neighbours would sit behind different L2s and every line would be fetched (or
 // written back partially) twice.  Default (1): such launches map adjacent tiles to the same XCD (measured on the T = 1
 // variant: 8.6 -> 10.2 G elements/s).  STARKHIP_XCD_SWZ (knobs.hpp): 0 = never, 2 = every tile pass (measured level for
-// T >= 4).
+// T >= 4).  The caller decides (xcd; knobs.hpp: shk_ntt_choose_cell); the grid is then padded to a multiple of 8 workgroups.
 
 // attr_done: one bit per device ordinal, per kernel instantiation (contexts on several devices, and on several host threads,
 // share the launcher)
 inline hipError_t shk_launch_tile_kernel(void (*k)(NttPassArgs), std::atomic<uint64_t>& attr_done, int log_t, unsigned threads,
-                                         size_t lds_bytes, const NttPassArgs& a, hipStream_t st) {
+                                         size_t lds_bytes, const NttPassArgs& a, bool xcd, hipStream_t st) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
@@ -539,8 +539,8 @@ inline hipError_t shk_launch_tile_kernel(void (*k)(NttPassArgs), std::atomic<uin
   if (tiles > 0x7ffffff0ull) return hipErrorInvalidValue;
   NttPassArgs b = a;
   uint64_t grid = tiles;
-  const int swz = shk_knobs().xcd_swz;
-  if (swz && (swz == 2 || log_t < 2) && tiles >= 64) {
+  b.xcd_per = 0;
+  if (xcd) {  // knobs.hpp: shk_ntt_choose_cell
     b.xcd_per = (uint32_t)((tiles + 7) / 8);
     grid = 8ull * b.xcd_per;
   }

@@ -1461,7 +1461,10 @@ def test_bench_rccl_collectives_with_one_rank(sa, workload):
     {"STARKHIP_TILE_LOGS": "11,9,10", "STARKHIP_TW2_MAX_LOG": "20"},  # a tile size per pass; small row tables (lookup fallback)
     {"STARKHIP_NTT_NARROW_TILES": "100000000"},                       # every pass of radix <= 2^10 in the one-butterfly-per-thread form
     {"STARKHIP_NTT_NARROW_TILES": "100000000", "STARKHIP_NTT_RADICES": "5,5,4,3", "STARKHIP_TW2_MAX_LOG": "12"},  # ... four passes of 2^17, lookups
-], ids=["7-7-6_swz2", "10-10_tile4096", "11-9", "6-6-4_tile2048", "per_pass_tiles", "narrow_everywhere", "narrow_5-5-4-3"])
+    {"STARKHIP_TILE_LOGS": "12,12,12", "STARKHIP_NTT_RADICES": "6,5,5"},  # 4096-element tiles of the small radices (2^16 in three passes)
+    {"STARKHIP_TILE_LOG": "9", "STARKHIP_TILE_LOG_BIG": "10"},            # 512-element tiles; 1024-element tiles of radix 2^9 and 2^10
+], ids=["7-7-6_swz2", "10-10_tile4096", "11-9", "6-6-4_tile2048", "per_pass_tiles", "narrow_everywhere", "narrow_5-5-4-3",
+        "6-5-5_tile4096", "tile512_big1024"])
 def test_alternate_ntt_plans_parity(sa, env):
     """Every decomposition the plan / tile knobs can select gives the same bytes: the NTT golden vectors (reference digests to
     2^20), every size against the oracle and the 2^22 / 2^24 digests, in a child process with the knobs set.  (The plan / tile
