@@ -118,6 +118,9 @@ def lib():
         "sh_lagrange_interp": (i32, [c_p, u8p, u8p, u64, c_p]),
         "sh_dev_poly_eval": (i32, [c_p, c_p, u64, u32, c_p, u64, c_p]),
         "sh_poly_eval": (i32, [c_p, u8p, u64, u32, u8p, u64, c_p]),
+        "sh_mod_ntt": (i32, [c_p, u8p, u8p, u64, c_p, u64, u32, u8p, i32]),
+        "sh_dev_mod_ntt": (i32, [c_p, u8p, c_p, c_p, u64, u32, u8p, i32]),
+        "sh_mod_mul_polys": (i32, [c_p, u8p, u8p, u64, u8p, u64, c_p, u64, u8p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares

@@ -209,3 +209,12 @@ hipError_t shk_pe_chunks(const fp* coefs, uint64_t n, uint64_t batch, uint64_t N
 hipError_t shk_pe_bcast_mul(fp* a, const fp* b, uint64_t rows, uint64_t len, hipStream_t st);
 // out[b][i] = sum_j leaves[b C + j][i] (x_i^N)^j, canonical
 hipError_t shk_pe_combine(const fp* leaves, const fp* xs, uint64_t m, uint64_t N, uint64_t C, uint64_t batch, fp* out, hipStream_t st);
+
+// ---- modntt.hip: the transform over any odd modulus below 2^256 (fft.py:256-345 with a run-time modulus; modntt_items.cuh) --------
+#include "modntt_items.cuh"
+// one tile pass of the plan (mn_pass); the modulus block is an argument of the launch
+hipError_t shk_mn_pass(const MnPass& a, const fpm_mod& M, hipStream_t st);
+// t.tw[e] = w^e in Montgomery form, e < t.count
+hipError_t shk_mn_tw(const MnTw& t, const fpm_mod& M, hipStream_t st);
+// out[i] = x[i] y[i] mod p, plain form, canonical
+hipError_t shk_mn_pointwise(const fpm* x, const fpm* y, fpm* out, uint64_t n, const fpm_mod& M, hipStream_t st);

@@ -19,6 +19,8 @@
 //   STARKHIP_WITNESS_GROUP=1|2|4|8|16  lanes per unit of the witness generator (witness.hip; default: chosen from the term table)
 //   STARKHIP_WITNESS_SLICE=k       steps per witness dispatch (default: about 2^13 sequential products per dispatch, at least 1)
 //   STARKHIP_EVAL_PATH=direct|tree  the path of every sh_poly_eval call (default: chosen per call, poly_items.cuh:pe_direct_preferred)
+//   STARKHIP_MODNTT_TILE_LOG=2..10 elements per tile (log2) of the generic transform (modntt_items.cuh; default 10): small values force
+//                                  plans of many passes at small n (tests/test_gpu_modntt.py)
 // All of them exist for the parity tests over alternate plans (tests/test_gpu_parity.py::test_alternate_ntt_plans_parity,
 // tools/stress_plans.py) and for A/B measurements; the defaults are the measured best.
 #pragma once
@@ -42,6 +44,7 @@ struct ShkKnobs {
   int witness_group = 0;     // 0: not given
   long witness_slice = 0;    // 0: not given
   int eval_path = 0;         // 0: chosen per call, 1: direct, 2: tree
+  int modntt_tile_log = 10;  // generic transform: 2 .. 10
 };
 
 namespace shk_knobs_detail {
@@ -93,6 +96,10 @@ inline void parse(ShkKnobs* k) {
   if (const char* e = getenv("STARKHIP_EVAL_PATH")) {
     const std::string v(e);
     k->eval_path = v == "direct" ? 1 : v == "tree" ? 2 : 0;
+  }
+  if (const char* e = getenv("STARKHIP_MODNTT_TILE_LOG")) {
+    const int v = atoi(e);
+    if (v >= 2 && v <= 10) k->modntt_tile_log = v;
   }
   if (const char* e = getenv("STARKHIP_NTT_RADICES")) {
     int r[4] = {0, 0, 0, 0}, cnt = 0, sum = 0;

@@ -8,11 +8,15 @@ The hot path -- the MiMC prime p = 2^256 - 351*2^32 + 1 with roots of unity of p
 call site of the reference (stark.py:31-34,217-225,253-256, fri.py:207-208,260-261) -- ALWAYS runs on the GPU through
 libstarkhip.so and raises when the library or the device is missing: there is no CPU fallback for it.
 
-Inputs the device code cannot represent at all -- another modulus (the reference's unit tests use Z/31,
-test_fft.py:98-113,132-149) or a root whose order is not a power of two (n = 6 there) -- are outside the hot path; for
-those `fft_1d` evaluates the transform directly on the host (`_host_dft`: Horner evaluation at every power of the
-root, O(n^2) on field elements, orders up to 2^12), so that the reference's unit tests run unchanged through this
-module.  It is never used for the MiMC field with a power-of-two order.
+Any other odd modulus below 2^256 (the BN254 or BLS12-381 scalar fields, Goldilocks, BabyBear, ...) with a root of power-of-two
+order runs on the GPU through the generic Montgomery path (sh_mod_ntt, sh_mod_mul_polys; `mod_ntt_bytes` is its wire-form entry and
+always runs on the device).  The call sites route there (`_mod_on_device`) when the order is at least 64 and either above 2^12 or
+the process already holds a device context -- the rule Polynomial.__call__ uses -- and return the same exact residues either way.
+
+What is left -- an even modulus, a root whose order is not a power of two (the reference's unit tests use Z/31 and n = 6,
+test_fft.py:98-113,132-149), small orders in a process that never touched the GPU -- `fft_1d` evaluates directly on the host
+(`_host_dft`: Horner evaluation at every power of the root, O(n^2) on field elements, orders up to 2^12), so that the reference's
+unit tests run unchanged through this module.  It is never used for the MiMC field with a power-of-two order.
 """
 import ctypes
 
@@ -66,6 +70,32 @@ def _on_device(modulus, root_of_unity):
 
 
 _HOST_MAX_ORDER = 1 << 12
+_MOD_MIN_ORDER = 64
+
+
+def _mod_on_device(modulus, root_of_unity):
+    """Another modulus goes to the generic device path when the device can take it (odd, below 2^256, a root of power-of-two order
+    of at least 64) and either the host transform could not (order above _HOST_MAX_ORDER) or this process already holds a context."""
+    m = int(modulus)
+    if m == MIMC_P or m < 3 or m % 2 == 0 or m >= 1 << 256:
+        return False
+    order = _lib.order_of_root(root_of_unity, m)
+    if order is None or order < _MOD_MIN_ORDER:
+        return False
+    return order > _HOST_MAX_ORDER or _lib._ctx is not None
+
+
+def mod_ntt_bytes(modulus, data, n, root_of_unity, inverse=False, batch=1):
+    """The transform over any odd modulus below 2^256 on the device (sh_mod_ntt): `data` = batch * n_in 32-byte big-endian values
+    (any 256-bit values) -> batch * n canonical outputs.  Always the device: raises without one."""
+    n_in = len(data) // (32 * batch)
+    if n_in > n:
+        raise ValueError("more input values (%d) than the order of the root of unity (%d)" % (n_in, n))
+    out = ctypes.create_string_buffer(32 * n * batch)
+    rc = _lib.lib().sh_mod_ntt(_lib.ctx(), int(modulus).to_bytes(32, "big"), bytes(data), n_in, out, n, batch,
+                               int(root_of_unity).to_bytes(32, "big"), 1 if inverse else 0)
+    _lib.check(rc, "sh_mod_ntt")
+    return out.raw
 
 
 def _host_dft(field, vals, modulus, root_of_unity, inv=False):
@@ -99,6 +129,11 @@ def _host_dft(field, vals, modulus, root_of_unity, inv=False):
 
 def fft_1d(field, vals, modulus, root_of_unity, inv=False):
     """starks/fft.py:316-331 -- the transform length is the order of root_of_unity; `vals` is zero-padded."""
+    if _mod_on_device(modulus, root_of_unity):
+        m = int(modulus)
+        vals = vals if isinstance(vals, (list, tuple, WireList)) else list(vals)
+        out = mod_ntt_bytes(m, _lib.to_wire(vals, m), _lib.order_of_root(root_of_unity, m), int(root_of_unity) % m, inverse=inv)
+        return _elements(field, out)
     if not _on_device(modulus, root_of_unity):
         return _host_dft(field, list(vals), modulus, root_of_unity, inv)
     n = _order(root_of_unity)
@@ -143,6 +178,17 @@ def mul_polys(a, b, root_of_unity):
                 break
     if field is None:
         field = IntegersModP(MIMC_P)
+    if _mod_on_device(field.p, root_of_unity):
+        m = int(field.p)
+        n = _lib.order_of_root(root_of_unity, m)
+        a, b = (a if isinstance(a, WireList) else list(a)), (b if isinstance(b, WireList) else list(b))
+        if len(a) > n or len(b) > n:
+            raise ValueError("operand longer than the order of the root of unity")
+        out = ctypes.create_string_buffer(32 * n)
+        rc = _lib.lib().sh_mod_mul_polys(_lib.ctx(), m.to_bytes(32, "big"), _lib.to_wire(a, m), len(a), _lib.to_wire(b, m), len(b), out, n,
+                                         (int(root_of_unity) % m).to_bytes(32, "big"))
+        _lib.check(rc, "sh_mod_mul_polys")
+        return _elements(field, out.raw)
     if not _on_device(field.p, root_of_unity):
         # another field or an order the device code does not cover: three direct transforms on the host (never the hot path)
         fa = _host_dft(field, list(a), field.p, root_of_unity)
