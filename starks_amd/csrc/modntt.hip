@@ -1,5 +1,5 @@
 // modntt.hip -- the kernels of the generic transform (sh_mod_ntt; modntt_items.cuh has the plan and the per-workgroup bodies,
-// capi.hip drives them).  One kernel runs any pass: a workgroup loads its tile into LDS, runs the tile's radix-2 stages with a
+// api_modntt.hip drives them).  One kernel runs any pass: a workgroup loads its tile into LDS, runs the tile's radix-2 stages with a
 // barrier between them and stores the tile.  The modulus block is a kernel argument of every launch.
 #include "internal.hpp"
 

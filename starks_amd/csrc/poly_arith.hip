@@ -1,5 +1,5 @@
 // poly_arith.hip -- the pointwise and per-node kernels of polynomial products, division, zpoly and lagrange_interp
-// (poly_items.cuh has the algebra; capi.hip drives the levels with batched NTT plans).  Every kernel is one thread per output
+// (poly_items.cuh has the algebra; api_poly.hip drives the levels with batched NTT plans).  Every kernel is one thread per output
 // element and memory-bound: a level moves its [nodes][2d] transforms through once.
 #include "internal.hpp"
 #include "poly_items.cuh"

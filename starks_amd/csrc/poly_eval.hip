@@ -1,5 +1,5 @@
 // poly_eval.hip -- the kernels of polynomial evaluation at arbitrary points (sh_poly_eval; poly_items.cuh has the element steps and
-// both drivers, capi.hip runs them).  The direct path: a small kernel builds each point's table of x^(2^b), the Horner kernel gives
+// both drivers, api_poly.hip runs them).  The direct path: a small kernel builds each point's table of x^(2^b), the Horner kernel gives
 // every workgroup's sum for its group of points, a second launch adds the workgroups.  The tree path's kernels: the chunks of the
 // coefficients reversed into rows, one transform multiplied into every row, the chunks combined per point.
 #include "internal.hpp"

@@ -1,5 +1,5 @@
 // poly_items.cuh -- the per-element and per-node steps of univariate polynomial arithmetic on the device (poly_arith.hip and
-// poly_eval.hip, driven from capi.hip): exact products, division with remainder, zpoly and lagrange_interp (starks/polynomial.py:
+// poly_eval.hip, driven from api_poly.hip): exact products, division with remainder, zpoly and lagrange_interp (starks/polynomial.py:
 // 116-150, starks/poly_utils.py:322-369), all built from batched cyclic NTTs of power-of-two sizes, and evaluation at arbitrary
 // points (polynomial.py:158-164; at the end of this file).
 //
@@ -24,7 +24,7 @@
 // r = a - q b on the low k - 1 coefficients.
 //
 // The element steps are __host__ __device__, and the drivers below are templates over an Ops back end that supplies the
-// transforms and the per-level launches: capi.hip's runs batched NTT plans and the poly_arith.hip kernels on the ctx stream,
+// transforms and the per-level launches: api_poly.hip's runs batched NTT plans and the poly_arith.hip kernels on the ctx stream,
 // tests/native/poly_tree_host.cpp's a textbook NTT and loops, so the host test runs this very driver and checks it against exact
 // integers.
 #pragma once

@@ -248,7 +248,7 @@ int sh_stark_verify(const uint8_t* proof, uint64_t proof_len, const uint8_t* inp
   if (!proof || !inputs || !outputs || !term_coefs || !term_exps || !term_counts || width == 0 || samples == 0) return SH_ERR_INVALID;
   if (steps < 2 || (steps & (steps - 1)) || ext < 2 || (ext & (ext - 1))) return SH_ERR_INVALID;
   if (steps >= (1ull << 24) || ext >= (1u << 24) || steps * ext >= (1ull << 24)) return SH_ERR_INVALID;  // utils.py:69 (no wrap-around)
-  if (width > SHK_STARK_MAX_WIDTH) return SH_ERR_UNSUPPORTED;  // as sh_stark_prove (capi.hip:stark_terms)
+  if (width > SHK_STARK_MAX_WIDTH) return SH_ERR_UNSUPPORTED;  // as sh_stark_prove (api_stark.hip:stark_terms)
   const uint64_t n = steps * ext;
   const uint32_t lg = (uint32_t)ilog2u(n), k = 3 * width;
   uint32_t degree = 0, begin = 0;
@@ -265,7 +265,7 @@ int sh_stark_verify(const uint8_t* proof, uint64_t proof_len, const uint8_t* inp
     coef[t] = f_from_wire(term_coefs + 32 * t);
     uint32_t sum = 0;
     for (uint32_t v = 0; v < width; ++v) sum += term_exps[(size_t)t * width + v];
-    if (sum > degree) degree = sum;  // as sh_stark_prove takes it (capi.hip:stark_terms): every listed term counts
+    if (sum > degree) degree = sum;  // as sh_stark_prove takes it (api_stark.hip:stark_terms): every listed term counts
   }
   Cursor cur{proof, proof_len};
   const uint8_t* m_root = cur.take(32);

@@ -1,6 +1,6 @@
 // witness.hip -- STARK witnesses on the device from any AIR's step polynomials (AIR.generate_witness, starks/air.py:32-52, 121-123).
 //
-// One dispatch writes rows [k0, k1) of every unit's [width][steps] witness; the host (capi.hip) launches the trace in such slices so that
+// One dispatch writes rows [k0, k1) of every unit's [width][steps] witness; the host (api_stark.hip) launches the trace in such slices so that
 // no dispatch walks an unbounded number of steps, each one resuming from the row the previous one wrote.  The step of one unit is split
 // over a group of G lanes of one wave (witness_items.cuh: wi_plan, wi_lane, wi_gather); 64 / G units share a wave and run the same
 // split, so their lanes take the same branches.  The term table of the system is staged in LDS once per dispatch, from the table

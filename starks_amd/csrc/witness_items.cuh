@@ -139,7 +139,7 @@ struct WitnessArgs {
   uint64_t k0, k1;      // rows of this dispatch
   uint32_t batch;
   uint32_t nterms;
-  const fp* coef;       // TermLayout::coef (capi.hip)
+  const fp* coef;       // TermLayout::coef (ctx.hpp)
   const uint8_t* exps;  // TermLayout::exps: rows of W + 1 bytes, the last one flags coef == 1
   uint32_t begin[SHK_STARK_MAX_WIDTH + 1];  // terms of dimension c: [begin[c], begin[c + 1])
   WiPlan plan;

@@ -1,7 +1,7 @@
 """FRI commit loop on the MI355X behind the reference's (commented-out) prime-field FRI driver,
 SmoothSubgroupFRI (starks/fri.py:176-366): NTT -> Merkle commit -> fold-by-4 at the challenge taken from
 the root -> Merkle commit -> sample 40 rows -> 5 branches per row, recursing on a domain 4x smaller until
-maxdeg_plus_1 <= 16.  The whole loop runs on the device (csrc/capi.hip:run_fri); one copy brings the flat
+maxdeg_plus_1 <= 16.  The whole loop runs on the device (csrc/api_fri.hip:run_fri); one copy brings the flat
 proof back and `unpack_proof` rebuilds the reference's nested lists.
 
     SmoothSubgroupFRI(field).generate_proximity_proof(f, root_of_unity, maxdeg_plus_1,

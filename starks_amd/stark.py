@@ -4,7 +4,7 @@
     proof = stark.mk_proof(witness, boundary)          # [m_root, l_root, branches, fri_proof]
     assert stark.verify_proof(proof, witness, boundary)
 
-`mk_proof` is one call into libstarkhip.so (sh_stark_prove, csrc/capi.hip:run_stark): low-degree extension, the
+`mk_proof` is one call into libstarkhip.so (sh_stark_prove, csrc/api_stark.hip:run_stark): low-degree extension, the
 constraint quotient D and boundary quotient B, the packed Merkle tree, the pseudorandom linear combination, the spot
 checks and the FRI commit all run on the device and one copy brings the flat proof back.  The reference builds D and B
 with O(n^2) coefficient arithmetic (stark.py:38-104); the device computes the same polynomials through the evaluation

@@ -1,5 +1,5 @@
 // Host driver of tests/test_modntt_host.py: fpm.cuh's arithmetic on files of wire-form operands, and the pass bodies of
-// modntt_items.cuh walked workgroup by workgroup, phase by phase, over the grid the library launches (capi.hip: mod_run).
+// modntt_items.cuh walked workgroup by workgroup, phase by phase, over the grid the library launches (api_modntt.hip: mod_run).
 //   consts <dir>                      mod -> out = p | r2 | one | n0inv (32 bytes each); exit 2: modulus rejected
 //   arith <dir> <op>                  mod, a, b -> out; op = mul add sub to_mont from_mont canon
 //   ntt <dir>                         mod, in, cases (lines "log_n n_in batch inverse tile_log offset root": the case reads batch n_in
@@ -37,7 +37,7 @@ static void put(std::vector<uint8_t>* o, const fpm& a) {
   o->insert(o->end(), w, w + 32);
 }
 
-// one transform exactly as capi.hip's mod_run issues it; src / dst are wire form
+// one transform exactly as api_modntt.hip's mod_run issues it; src / dst are wire form
 static int walk(const fpm_mod& M, const fpm& root_mont, const fpm& scale, int log_n, int tile_log, const uint8_t* src, uint64_t n_in,
                 uint8_t* dst, uint64_t batch) {
   const uint64_t n = 1ull << log_n;

@@ -1,5 +1,5 @@
 // Both drivers of polynomial evaluation (starks_amd/csrc/poly_items.cuh: pa_eval with pa_eval_direct and pa_eval_tree -- the code
-// capi.hip runs) on a host back end: a textbook radix-2 NTT over 7^((p - 1) / m) in place of the device plans, and one loop per
+// api_poly.hip runs) on a host back end: a textbook radix-2 NTT over 7^((p - 1) / m) in place of the device plans, and one loop per
 // kernel launch over the same element steps, the direct path's workgroups summed lane by lane as poly_eval.hip's direct_kernel does.
 // tests/test_poly_eval_host.py compares the results with exact integers.
 //   poly_eval_host direct|tree DIR BATCH     DIR/coefs ([BATCH][n]), DIR/xs ([m])  ->  DIR/out ([BATCH][m])

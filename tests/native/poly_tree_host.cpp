@@ -1,5 +1,5 @@
 // The device polynomial arithmetic's drivers (starks_amd/csrc/poly_items.cuh: pa_mul, pa_divmod, pa_zpoly, pa_lagrange -- the code
-// capi.hip runs) on a host back end: a textbook radix-2 NTT over 7^((p - 1) / m) in place of the device plans, and one loop per kernel
+// api_poly.hip runs) on a host back end: a textbook radix-2 NTT over 7^((p - 1) / m) in place of the device plans, and one loop per kernel
 // launch over the same element steps.  tests/test_poly_arith_host.py compares the results with exact integers.
 //   poly_tree_host mul DIR        DIR/a, DIR/b        -> DIR/out        (n_a + n_b - 1 coefficients)
 //   poly_tree_host divmod DIR     DIR/a, DIR/b        -> DIR/q, DIR/r

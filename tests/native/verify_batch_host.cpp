@@ -138,7 +138,7 @@ int main(int argc, char** argv) {
     memcpy(counts.data(), cb.data(), cb.size());
     rc = vb_plan_stark_proof(&p, steps, ext, width, exps.data(), counts.data(), samples);
     if (rc == SH_OK) {
-      // the device layout of the terms (capi.hip:stark_terms): limb-form coefficients, exponent rows of width + 1 bytes
+      // the device layout of the terms (api_stark.hip:stark_terms): limb-form coefficients, exponent rows of width + 1 bytes
       const uint32_t total = (uint32_t)(coefs.size() / 32);
       for (uint32_t t = 0; t < total; ++t) coef.push_back(vb_wire(&coefs[32 * t]));
       rows.assign((size_t)total * (width + 1), 0);

@@ -561,7 +561,7 @@ def compose(vals, radices, w, inverse=False, src_n=0):
     """the reference passes over a plan (log2 radices, first pass first; n = their product >= 4): pass d < m is a column pass with P =
     the product of the radices before it, S = n / (P R), tw(k, j2) = (w^P)^(j2 k) and wR = w^(n / R); the last is the row pass with the
     earlier radices as digits.  inverse: over w^-1, times n^-1 -- the row pass's scale in a one-pass plan, else folded into the first
-    pass's twiddles (capi.hip: get_plan).  src_n: vals holds the first src_n elements, the rest is zero."""
+    pass's twiddles (api_ntt.hip: get_plan).  src_n: vals holds the first src_n elements, the rest is zero."""
     log_n = sum(radices)
     n = 1 << log_n
     root = pow(w, n - 1, P) if inverse else w

@@ -322,6 +322,44 @@ def test_plan_cache(L):
         L.sh_ctx_destroy(c)
 
 
+def test_plan_cache_holds_both_kinds_of_plan(L):
+    """a MiMC transform's plan and a generic-modulus table in one context share one cache: one count, one byte total, one LRU order.
+    The MiMC plan's size is whatever the first statistics reading says; the 2^12-point table is 2^11 powers of 32 bytes."""
+    from oracle import pyoracle
+    from starks_amd import _lib
+    c = ctypes.c_void_p()
+    assert L.sh_ctx_create(_lib.default_device(), ctypes.byref(c)) == OK
+    try:
+        n, table = 1 << 12, 32 << 11
+        P, p = mc.MIMC_P, MODULI["bn254"]
+        wm, wb = root_of("mimc", n), root_of("bn254", n)
+        xm, xb = [v % P for v in mc.inputs(21, n, P)], mc.inputs(22, n, p)
+        want_m, want_b = pyoracle.fft_1d(xm, P, wm), mc.transform(xb, n, p, wb)
+
+        def mimc_ntt():
+            out = ctypes.create_string_buffer(32 * n)
+            assert L.sh_ntt(c, wire(xm), n, out, n, b32(wm), 0) == OK, L.sh_last_error(c)
+            return ints(out.raw)
+
+        assert _stats(L, c) == [0, 0, 0, 0]
+        assert mimc_ntt() == want_m
+        first = _stats(L, c)
+        mimc = first[1]
+        assert first == [1, mimc, 1, 0] and mimc > 0 and mimc != table
+        assert mod_ntt(L, p, xb, n, wb, ctx=c) == want_b
+        assert _stats(L, c) == [2, mimc + table, 2, 0]
+        assert mimc_ntt() == want_m  # a hit: nothing is built, and the table is now the least recently used of the two
+        assert _stats(L, c) == [2, mimc + table, 2, 0]
+        assert L.sh_ctx_set_plan_budget(c, mimc + table - 1) == OK  # one byte short of both: this entry evicts the table alone
+        assert _stats(L, c) == [1, mimc, 2, 1]
+        assert mimc_ntt() == want_m  # still a hit
+        assert _stats(L, c) == [1, mimc, 2, 1]
+        assert mod_ntt(L, p, xb, n, wb, ctx=c) == want_b  # built again, beside the MiMC plan
+        assert _stats(L, c) == [2, mimc + table, 3, 1]
+    finally:
+        L.sh_ctx_destroy(c)
+
+
 # ---- 8. Python call sites ------------------------------------------------------------------------------------------------------------
 def test_python_call_sites(L):
     from starks_amd import IntegersModP, _lib, fft

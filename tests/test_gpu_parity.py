@@ -1260,7 +1260,7 @@ def test_mimc_unit_generator_status_batch_and_trim(sa, oracle):
 
 def test_pinned_batch_transform_is_pipelined_and_identical(sa, oracle):
     """sh_ntt_batch from page-locked buffers moves its vectors through in chunks (upload / transform / download overlapped on
-    three streams, csrc/capi.hip:ntt_batch_pipelined): every vector must equal the one-at-a-time result and the oracle's."""
+    three streams, csrc/api_ntt.hip:ntt_batch_pipelined): every vector must equal the one-at-a-time result and the oracle's."""
     import random
     rng = random.Random(3)
     n, B = 1 << 15, 5   # 5 MiB: above the pipelining threshold, a chunk count that does not divide evenly into 8
@@ -1293,7 +1293,7 @@ def test_pinned_batch_transform_is_pipelined_and_identical(sa, oracle):
 
 def test_plan_cache_is_lru_with_a_byte_budget(sa, oracle):
     """200 distinct (n, root) shapes interleaved with a repeated hot shape under a budget that holds only a few plans: the
-    hot shape is built once and never rebuilt (least-recently-used eviction, csrc/capi.hip:evict_plans), the held bytes stay
+    hot shape is built once and never rebuilt (least-recently-used eviction, csrc/ctx.hip:evict_plans), the held bytes stay
     inside the budget + one call's tables, and every transform still equals the oracle's."""
     import ctypes, random
     L = sa.lib.lib()

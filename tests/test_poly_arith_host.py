@@ -1,6 +1,6 @@
 """The device polynomial arithmetic's decomposition (starks_amd/csrc/poly_items.cuh) run on the host by
 tests/native/poly_tree_host.cpp (hipcc): the same padded product tree, Newton inverses, scaled remainder tree and numerator tree as
-capi.hip drives on the GPU, every level a batch of size-2d transforms, at n ~ 10^3 -- against exact Python-int schoolbook products,
+api_poly.hip drives on the GPU, every level a batch of size-2d transforms, at n ~ 10^3 -- against exact Python-int schoolbook products,
 long division, zpoly and O(n^2) Lagrange, and against tests/golden/poly_arith.json (the live reference's outputs).  CPU only."""
 import os
 import random
