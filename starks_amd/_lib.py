@@ -121,6 +121,11 @@ def lib():
         "sh_mod_ntt": (i32, [c_p, u8p, u8p, u64, c_p, u64, u32, u8p, i32]),
         "sh_dev_mod_ntt": (i32, [c_p, u8p, c_p, c_p, u64, u32, u8p, i32]),
         "sh_mod_mul_polys": (i32, [c_p, u8p, u8p, u64, u8p, u64, c_p, u64, u8p]),
+        "sh_dev_mod64_ntt": (i32, [c_p, u64, c_p, u64, c_p, u64, u32, u64, i32]),
+        "sh_mod64_ntt": (i32, [c_p, u64, c_p, u64, c_p, u64, u32, u64, i32]),
+        "sh_mod64_mul_polys": (i32, [c_p, u64, c_p, u64, c_p, u64, c_p, u64, u64]),
+        "sh_dev_mod64_from_limbs": (i32, [c_p, u64, c_p, c_p, u64]),
+        "sh_dev_mod64_to_limbs": (i32, [c_p, c_p, c_p, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares

@@ -218,3 +218,15 @@ hipError_t shk_mn_pass(const MnPass& a, const fpm_mod& M, hipStream_t st);
 hipError_t shk_mn_tw(const MnTw& t, const fpm_mod& M, hipStream_t st);
 // out[i] = x[i] y[i] mod p, plain form, canonical
 hipError_t shk_mn_pointwise(const fpm* x, const fpm* y, fpm* out, uint64_t n, const fpm_mod& M, hipStream_t st);
+
+// ---- ntt64.hip: the transform over any odd modulus below 2^64 on packed 64-bit words (ntt64_items.cuh) ------------------------------
+#include "ntt64_items.cuh"
+// one tile pass of the plan (n64_pass); the modulus block is an argument of the launch
+hipError_t shk_n64_pass(const N64Pass& a, const f64_mod& M, hipStream_t st);
+// t.tab = lo | hi | stw, Montgomery form (n64_tw_item)
+hipError_t shk_n64_tw(const N64Tw& t, const f64_mod& M, hipStream_t st);
+// out[i] = x[i] y[i] mod p, plain form, canonical
+hipError_t shk_n64_pointwise(const uint64_t* x, const uint64_t* y, uint64_t* out, uint64_t n, const f64_mod& M, hipStream_t st);
+// words[i] = (8 x u32 limbs i) mod p; limbs[i] = words[i] zero-extended
+hipError_t shk_n64_from_limbs(const void* limbs, uint64_t* words, uint64_t count, const f64_mod& M, hipStream_t st);
+hipError_t shk_n64_to_limbs(const uint64_t* words, void* limbs, uint64_t count, hipStream_t st);

@@ -21,6 +21,9 @@
 //   STARKHIP_EVAL_PATH=direct|tree  the path of every sh_poly_eval call (default: chosen per call, poly_items.cuh:pe_direct_preferred)
 //   STARKHIP_MODNTT_TILE_LOG=2..10 elements per tile (log2) of the generic transform (modntt_items.cuh; default 10): small values force
 //                                  plans of many passes at small n (tests/test_gpu_modntt.py)
+//   STARKHIP_MOD64_TILE_LOG=2..13  elements per tile (log2) of the packed-word transform (ntt64_items.cuh; default 12); the largest
+//                                  radix log of a plan is t - min(4, t / 2) (tests/test_gpu_ntt64.py); 12 against 13:
+//                                  tools/mod64_ntt_time.py, profiles/r12_mod64_ntt.json
 // All of them exist for the parity tests over alternate plans (tests/test_gpu_parity.py::test_alternate_ntt_plans_parity,
 // tools/stress_plans.py) and for A/B measurements; the defaults are the measured best.
 #pragma once
@@ -45,6 +48,7 @@ struct ShkKnobs {
   long witness_slice = 0;    // 0: not given
   int eval_path = 0;         // 0: chosen per call, 1: direct, 2: tree
   int modntt_tile_log = 10;  // generic transform: 2 .. 10
+  int mod64_tile_log = 12;   // packed-word transform: 2 .. 13
 };
 
 namespace shk_knobs_detail {
@@ -100,6 +104,10 @@ inline void parse(ShkKnobs* k) {
   if (const char* e = getenv("STARKHIP_MODNTT_TILE_LOG")) {
     const int v = atoi(e);
     if (v >= 2 && v <= 10) k->modntt_tile_log = v;
+  }
+  if (const char* e = getenv("STARKHIP_MOD64_TILE_LOG")) {
+    const int v = atoi(e);
+    if (v >= 2 && v <= 13) k->mod64_tile_log = v;
   }
   if (const char* e = getenv("STARKHIP_NTT_RADICES")) {
     int r[4] = {0, 0, 0, 0}, cnt = 0, sum = 0;

@@ -13,12 +13,17 @@ order runs on the GPU through the generic Montgomery path (sh_mod_ntt, sh_mod_mu
 always runs on the device).  The call sites route there (`_mod_on_device`) when the order is at least 64 and either above 2^12 or
 the process already holds a device context -- the rule Polynomial.__call__ uses -- and return the same exact residues either way.
 
+The small fields -- any odd modulus below 2^64: Goldilocks, BabyBear, KoalaBear, ... -- also have a path of their own on packed
+64-bit words (`mod64_ntt`, `mod64_mul_polys`: sh_mod64_ntt, 8 bytes per element instead of 32; always the device).  The call sites
+above do not route there: they keep the 32-byte path for every modulus.
+
 What is left -- an even modulus, a root whose order is not a power of two (the reference's unit tests use Z/31 and n = 6,
 test_fft.py:98-113,132-149), small orders in a process that never touched the GPU -- `fft_1d` evaluates directly on the host
 (`_host_dft`: Horner evaluation at every power of the root, O(n^2) on field elements, orders up to 2^12), so that the reference's
 unit tests run unchanged through this module.  It is never used for the MiMC field with a power-of-two order.
 """
 import ctypes
+import struct
 
 from . import _lib
 from ._lib import MIMC_P
@@ -96,6 +101,63 @@ def mod_ntt_bytes(modulus, data, n, root_of_unity, inverse=False, batch=1):
                                int(root_of_unity).to_bytes(32, "big"), 1 if inverse else 0)
     _lib.check(rc, "sh_mod_ntt")
     return out.raw
+
+
+def _words(data):
+    """a buffer of native 8-byte words (bytes, array('Q'), a numpy uint64 array, ...) or a sequence of ints -> (what ctypes passes as
+    the pointer, the object that keeps it alive, the word count)"""
+    if isinstance(data, (list, tuple)):
+        data = struct.pack("=%dQ" % len(data), *[int(v) for v in data])
+    if not isinstance(data, bytes):
+        mv = memoryview(data)
+        if mv.format not in ("B", "b", "c", "<B", "@B") and (mv.itemsize != 8 or mv.format.lstrip("@=<")[-1:] not in ("Q", "L")):
+            raise TypeError("mod64: a buffer of bytes or of unsigned 8-byte words is needed (got format %r)" % mv.format)
+        if mv.nbytes % 8:
+            raise ValueError("the data is not a whole number of 8-byte words")
+        try:
+            buf = (ctypes.c_char * mv.nbytes).from_buffer(mv)  # no copy: a writable contiguous buffer
+            return buf, mv, mv.nbytes // 8
+        except (TypeError, ValueError, BufferError):
+            data = mv.tobytes()
+    if len(data) % 8:
+        raise ValueError("the data is not a whole number of 8-byte words")
+    return data, data, len(data) // 8
+
+
+def _word_result(count):
+    out = bytearray(8 * count)
+    return out, (ctypes.c_char * len(out)).from_buffer(out)
+
+
+def mod64_ntt(modulus, data, n, root_of_unity, inverse=False, batch=1):
+    """The transform over any odd modulus below 2^64 on the device (sh_mod64_ntt): `data` = batch * n_in native 8-byte words (any
+    buffer of them, or a sequence of ints; any 64-bit values) -> batch * n canonical outputs, a memoryview of format 'Q' over a fresh
+    bytearray.  Always the device: raises without one."""
+    src, _keep, count = _words(data)
+    if batch < 1 or count % batch:
+        raise ValueError("%d words are not %d vectors of equal length" % (count, batch))
+    n_in = count // batch
+    if n_in > n:
+        raise ValueError("more input values (%d) than the order of the root of unity (%d)" % (n_in, n))
+    out, dst = _word_result(n * batch)
+    rc = _lib.lib().sh_mod64_ntt(_lib.ctx(), int(modulus), src, n_in, dst, n, batch, int(root_of_unity), 1 if inverse else 0)
+    _lib.check(rc, "sh_mod64_ntt")
+    del dst
+    return memoryview(out).cast("Q")
+
+
+def mod64_mul_polys(modulus, a, b, n, root_of_unity):
+    """mul_polys over any odd modulus below 2^64 on the device (sh_mod64_mul_polys): n * (a b mod x^n - 1), unscaled exactly like the
+    reference; operands and result as in `mod64_ntt`."""
+    sa, _ka, na = _words(a)
+    sb, _kb, nb = _words(b)
+    if na > n or nb > n:
+        raise ValueError("operand longer than the order of the root of unity")
+    out, dst = _word_result(n)
+    rc = _lib.lib().sh_mod64_mul_polys(_lib.ctx(), int(modulus), sa, na, sb, nb, dst, n, int(root_of_unity))
+    _lib.check(rc, "sh_mod64_mul_polys")
+    del dst
+    return memoryview(out).cast("Q")
 
 
 def _host_dft(field, vals, modulus, root_of_unity, inv=False):
