@@ -47,23 +47,32 @@ uint64_t fri_proof_len(uint64_t n, uint64_t maxdeg_plus_1, uint32_t samples) {
   return total + 32 * n;
 }
 
-// every round's parameters are checked before anything is launched
-int fri_validate(uint64_t n, uint64_t maxdeg_plus_1, uint32_t exclude, uint32_t samples) {
+// every round's parameters are checked before anything is launched; `why`, when given, receives the reason of a refusal
+int fri_validate(uint64_t n, uint64_t maxdeg_plus_1, uint32_t exclude, uint32_t samples, const char** why) {
+  const char* sink = "";
+  const char*& reason = why ? *why : sink;
   uint64_t nn = n, md = maxdeg_plus_1;
   bool first = true;
   uint32_t rounds = 0;
   while (md > 16) {
+    reason = "more rounds than a commit holds (SHK_FRI_MAX_ROUNDS)";
     if (++rounds > SHK_FRI_MAX_ROUNDS) return SH_ERR_UNSUPPORTED;  // FriSampleArgs holds that many rounds (checked BEFORE any launch)
+    reason = "a round with fewer than 16 points (maxdeg_plus_1 is too large for n)";
     if (nn < 16) return SH_ERR_INVALID;            // the reference cannot merkelize a column of < 4 values
+    reason = "a column of 2^24 rows or more cannot be sampled (utils.py:69)";
     if ((nn >> 2) >= (1ull << 24)) return SH_ERR_UNSUPPORTED;  // assert modulus < 2**24 (utils.py:69)
     const uint32_t s = first ? samples : 40;
+    reason = "samples must be at least 1";
     if (s == 0) return SH_ERR_INVALID;
+    reason = "exclude_multiples_of = 1 divides by zero in the reference (utils.py:90)";
     if (exclude == 1) return SH_ERR_INVALID;       // division by zero in the reference (utils.py:90)
+    reason = "exclude_multiples_of leaves no row to sample";
     if (exclude && ((nn >> 2) * (exclude - 1)) / exclude == 0) return SH_ERR_INVALID;
     nn >>= 2;
     md >>= 2;
     first = false;
   }
+  reason = "";
   return SH_OK;
 }
 

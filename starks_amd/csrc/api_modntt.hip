@@ -2,33 +2,30 @@
 #include "ctx.hpp"
 using namespace shk;
 
-namespace {
-// everything the host derives from (modulus, root, n, direction) before a launch; nothing here touches the device
-struct ModCall {
-  fpm_mod M;
-  fpm root_mont;  // the effective root (inverted for an inverse transform), Montgomery form
-  fpm scale;      // plain form: 1, or n^-1 for an inverse
-  int log_n;
-};
-
+namespace shk {
+// (ctx.hpp has ModCall and the three declarations: the commit over another modulus, api_modfri.hip, transforms with them)
 int mod_prepare(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint64_t n, uint64_t batch, bool inverse, bool scaled,
-                ModCall* mc) {
-  if (!is_pow2(n) || batch == 0) return SH_ERR_INVALID;
+                ModCall* mc, const char* who) {
+  const std::string pre = std::string(who) + ": ";
+  if (!is_pow2(n) || batch == 0) {
+    c->err = pre + "n must be a power of two and batch at least 1";
+    return SH_ERR_INVALID;
+  }
   if (n > (1ull << MN_MAX_LOG_N) || batch > (1ull << MN_MAX_LOG_N) || batch * n > (1ull << MN_MAX_LOG_N)) {
-    c->err = "sh_mod_ntt: n and batch * n are limited to 2^26";
+    c->err = pre + "n and batch * n are limited to 2^26";
     return SH_ERR_UNSUPPORTED;
   }
   if (!fpm_mod_init(modulus, &mc->M)) {
-    c->err = "sh_mod_ntt: the modulus must be odd and at least 3";
+    c->err = pre + "the modulus must be odd and at least 3";
     return SH_ERR_INVALID;
   }
   const fpm w = fpm_from_wire_bytes(root);
   if (!fpm_below_p(w, mc->M)) {
-    c->err = "sh_mod_ntt: root is not below the modulus";
+    c->err = pre + "root is not below the modulus";
     return SH_ERR_ROOT_ORDER;
   }
   if (!mn_check_root(w, n, mc->M)) {
-    c->err = "sh_mod_ntt: root does not have order n in this ring";
+    c->err = pre + "root does not have order n in this ring";
     return SH_ERR_ROOT_ORDER;
   }
   mc->log_n = ilog2(n);
@@ -92,7 +89,7 @@ int mod_run(sh_ctx* c, const ModCall& mc, const fpm* tw, const void* src, uint64
   }
   return SH_OK;
 }
-}  // namespace
+}  // namespace shk
 
 extern "C" {
 

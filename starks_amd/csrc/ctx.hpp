@@ -201,10 +201,27 @@ struct FriBuffers {
   uint32_t *tree, *tree2, *ys;
 };
 uint64_t fri_proof_len(uint64_t n, uint64_t maxdeg_plus_1, uint32_t samples);
-int fri_validate(uint64_t n, uint64_t maxdeg_plus_1, uint32_t exclude, uint32_t samples);
+int fri_validate(uint64_t n, uint64_t maxdeg_plus_1, uint32_t exclude, uint32_t samples, const char** why = nullptr);
 int fri_buffers(sh_ctx* c, uint64_t n, uint32_t batch, uint32_t samples, FriBuffers* b);
 int fri_rounds(sh_ctx* c, NttPlan* pl, FriBuffers fb, uint64_t n, uint64_t maxdeg_plus_1, uint32_t exclude, uint32_t samples,
                uint32_t batch, uint8_t* d_proof, uint64_t stride, bool have_tree);
+
+// ---- api_modntt.hip -------------------------------------------------------------------------------------
+// everything the host derives from (modulus, root, n, direction) before a launch; nothing here touches the device
+struct ModCall {
+  fpm_mod M;
+  fpm root_mont;  // the effective root (inverted for an inverse transform), Montgomery form
+  fpm scale;      // plain form: 1, or n^-1 for an inverse
+  int log_n;
+};
+// every check of a generic-modulus call, on the host; `who` opens the sh_last_error text
+int mod_prepare(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint64_t n, uint64_t batch, bool inverse, bool scaled,
+                ModCall* mc, const char* who = "sh_mod_ntt");
+// the table of (modulus, effective root, n): w^e in Montgomery form, e < n / 2, held in the plan cache
+int mod_table(sh_ctx* c, const ModCall& mc, const fpm** out);
+// src [batch][n_in] (wire form when wire_in) -> dst [batch][n] (wire form when wire_out); src may be dst when n_in == n
+int mod_run(sh_ctx* c, const ModCall& mc, const fpm* tw, const void* src, uint64_t n_in, void* dst, uint32_t batch, bool wire_in,
+            bool wire_out);
 
 // ---- api_stark.hip --------------------------------------------------------------------------------------
 // Device layout of the step-polynomial description (one allocation, ctx->terms_dev)

@@ -114,6 +114,9 @@ hipError_t shk_fri_sample_and_gather_all(const FriSampleArgs& a, hipStream_t st)
 // trees are tree_words u32 apart
 hipError_t shk_sample_indices(const uint32_t* d_nodes, uint64_t tree_words, uint32_t modulus, uint32_t batch,
                               uint32_t samples, uint32_t exclude, uint32_t* d_ys, hipStream_t st);
+// the sampling launch of shk_fri_sample_and_gather_all alone (reads r[].nodes_m2, n, samples, ys_off; batch, exclude, ys): the commit
+// over another modulus samples with it and gathers with its own kernel (modfri.hip)
+hipError_t shk_fri_sample_all(const FriSampleArgs& a, hipStream_t st);
 
 // ---- stark.hip: constraint / boundary quotients, packed tree, linear combination, spot checks (stark.py:233-279) ----
 constexpr uint32_t SHK_STARK_MAX_WIDTH = 9;  // get_pseudorandom_ks returns None from 10 on (stark.py:106-126)
@@ -218,6 +221,17 @@ hipError_t shk_mn_pass(const MnPass& a, const fpm_mod& M, hipStream_t st);
 hipError_t shk_mn_tw(const MnTw& t, const fpm_mod& M, hipStream_t st);
 // out[i] = x[i] y[i] mod p, plain form, canonical
 hipError_t shk_mn_pointwise(const fpm* x, const fpm* y, fpm* out, uint64_t n, const fpm_mod& M, hipStream_t st);
+
+// ---- modfri.hip: the FRI commit over any odd modulus below 2^256 (fri.py:189-266; modfri_items.cuh, which the two files that use
+// these include themselves: it brings blake2s.cuh) -------------------------------------------------------------------------------------
+struct MfTree;
+struct MfFold;
+struct MfGather;
+// the leaf-kernel levels of the trees of t.values: nodes [n/4, n), and [n, 2n) when store_leaves; shk_merkle_upper_levels does the rest
+hipError_t shk_mf_leaves(const MfTree& t, hipStream_t st);
+// a.column = the fold of a.values, one thread per row
+hipError_t shk_mf_fold(const MfFold& a, const fpm_mod& M, hipStream_t st);
+hipError_t shk_mf_gather(const MfGather& a, hipStream_t st);
 
 // ---- ntt64.hip: the transform over any odd modulus below 2^64 on packed 64-bit words (ntt64_items.cuh) ------------------------------
 #include "ntt64_items.cuh"

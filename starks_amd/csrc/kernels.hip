@@ -657,6 +657,11 @@ hipError_t shk_fri_sample_and_gather_all(const FriSampleArgs& a, hipStream_t st)
   hipLaunchKernelGGL(fri_gather_all_kernel, dim3(grid_for(a.work_total + a.final_n * a.batch)), dim3(TPB), 0, st, a);
   return hipGetLastError();
 }
+hipError_t shk_fri_sample_all(const FriSampleArgs& a, hipStream_t st) {
+  if (!a.batch || !a.rounds) return hipSuccess;
+  hipLaunchKernelGGL(fri_sample_all_kernel, dim3((a.batch + 15) / 16, a.rounds), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
 hipError_t shk_merkelize_packed(const uint8_t* d_evals, uint64_t n, uint32_t k, uint8_t* d_leaves, uint32_t* d_nodes,
                                 hipStream_t st) {
   if (n < 4 || (n & (n - 1)) || k == 0) return hipErrorInvalidValue;

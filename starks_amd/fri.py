@@ -1,5 +1,6 @@
 """FRI commit loop on the MI355X behind the reference's (commented-out) prime-field FRI driver,
-SmoothSubgroupFRI (starks/fri.py:176-366): NTT -> Merkle commit -> fold-by-4 at the challenge taken from
+SmoothSubgroupFRI (starks/fri.py:176-366), over the MiMC prime (sh_fri_prove) and over any other odd modulus below 2^256
+(sh_mod_fri_prove): NTT -> Merkle commit -> fold-by-4 at the challenge taken from
 the root -> Merkle commit -> sample 40 rows -> 5 branches per row, recursing on a domain 4x smaller until
 maxdeg_plus_1 <= 16.  The whole loop runs on the device (csrc/api_fri.hip:run_fri); one copy brings the flat
 proof back and `unpack_proof` rebuilds the reference's nested lists.
@@ -70,25 +71,50 @@ def prove_flat(coeff_bytes, n, root_of_unity, maxdeg_plus_1, exclude_multiples_o
     return out.raw
 
 
-def prove_low_degree(f, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0, fri_spot_check_security_factor=40):
-    """fri.py:189-266.  `f`: a Poly (its .coefficients) or a list of coefficients."""
+def mod_prove_flat(modulus, coeff_bytes, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0, samples=40, batch=1):
+    """prove_flat over any odd modulus below 2^256 (sh_mod_fri_prove): coeff_bytes = batch * n_coeffs wire-form coefficients, any
+    256-bit value is taken modulo `modulus` -> batch flat proofs in prove_flat's layout and length."""
+    n_coeffs = len(coeff_bytes) // (32 * batch)
+    plen = proof_len(n, maxdeg_plus_1, samples)
+    out = ctypes.create_string_buffer(plen * batch)
+    rc = _lib.lib().sh_mod_fri_prove(_lib.ctx(), int(modulus).to_bytes(32, "big"), coeff_bytes, n_coeffs, n,
+                                     int(root_of_unity).to_bytes(32, "big"), maxdeg_plus_1, exclude_multiples_of, samples, batch, out,
+                                     plen * batch)
+    _lib.check(rc, "sh_mod_fri_prove")
+    return out.raw
+
+
+def _field_modulus(coeffs, field):
+    """the modulus the coefficients live in: the WireList's field, the first coefficient's, the driver's own, else the MiMC prime"""
+    if isinstance(coeffs, WireList):
+        return int(coeffs.field.p)
+    for c in coeffs:
+        if hasattr(c, "p"):
+            return int(c.p)
+        break
+    return int(field.p) if field is not None else MIMC_P
+
+
+def prove_low_degree(f, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0, fri_spot_check_security_factor=40, field=None):
+    """fri.py:189-266.  `f`: a Poly (its .coefficients) or a list of coefficients.  The MiMC prime runs sh_fri_prove; any other odd
+    modulus below 2^256 under a root of power-of-two order runs sh_mod_fri_prove; anything else is not accelerated."""
     coeffs = f.coefficients if hasattr(f, "coefficients") else f
-    if isinstance(coeffs, WireList):  # e.g. an inverse transform's output: the bytes go to the prover as they are
-        if int(coeffs.field.p) != MIMC_P:
-            raise NotImplementedError("starks_amd accelerates the MiMC prime field only")
-    else:
+    if not isinstance(coeffs, WireList):  # a WireList (e.g. an inverse transform's output) goes to the prover as the bytes it is
         coeffs = list(coeffs)
-        for c in coeffs:
-            if hasattr(c, "p") and int(c.p) != MIMC_P:
-                raise NotImplementedError("starks_amd accelerates the MiMC prime field only")
-            break
-    n = _lib.order_of_root(root_of_unity)
+    p = _field_modulus(coeffs, field)
+    if p != MIMC_P and (p < 3 or p % 2 == 0 or p >> 256):
+        raise NotImplementedError("starks_amd accelerates odd moduli below 2^256 only")
+    n = _lib.order_of_root(root_of_unity, p)
     if n is None:
         raise NotImplementedError("root_of_unity must have power-of-two order")
     if len(coeffs) > n:
         raise ValueError("polynomial has more coefficients than the evaluation domain has points")
-    flat = prove_flat(_lib.to_wire(coeffs), n, int(root_of_unity), maxdeg_plus_1, exclude_multiples_of,
-                      fri_spot_check_security_factor)
+    if p == MIMC_P:
+        flat = prove_flat(_lib.to_wire(coeffs), n, int(root_of_unity), maxdeg_plus_1, exclude_multiples_of,
+                          fri_spot_check_security_factor)
+    else:
+        flat = mod_prove_flat(p, _lib.to_wire(coeffs, p), n, int(root_of_unity) % p, maxdeg_plus_1, exclude_multiples_of,
+                              fri_spot_check_security_factor)
     return unpack_proof(flat, n, maxdeg_plus_1, fri_spot_check_security_factor)
 
 
@@ -197,7 +223,8 @@ class SmoothSubgroupFRI(object):
 
     def generate_proximity_proof(self, f, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0,
                                  fri_spot_check_security_factor=40):
-        return prove_low_degree(f, root_of_unity, maxdeg_plus_1, exclude_multiples_of, fri_spot_check_security_factor)
+        return prove_low_degree(f, root_of_unity, maxdeg_plus_1, exclude_multiples_of, fri_spot_check_security_factor,
+                                field=self.field)
 
     def verify_proximity_proof(self, proof, merkle_root, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0,
                                fri_spot_check_security_factor=40):
