@@ -12,8 +12,8 @@ template <int LOG_R, bool LAST, int TILE_LOG>
 hipError_t launch_tile(const NttPassArgs& a, bool xcd, hipStream_t st) {
   constexpr int LOG_T = TILE_LOG - LOG_R;
   static std::atomic<uint64_t> attr_done{0};
-  return shk_launch_tile_kernel(ntt_pass_kernel<LOG_R, LOG_T, LAST>, attr_done, LOG_T, 1u << (TILE_LOG - 2), (size_t)32 << TILE_LOG,
-                                a, xcd, st);
+  return shk_launch_tile_kernel(ntt_pass_kernel<LOG_R, LOG_T, LAST>, attr_done, LOG_T, 1u << (TILE_LOG - 2),
+                                tile_lds_bytes<LOG_R, LOG_T>(), a, xcd, st);
 }
 
 // narrow launches (ntt_kernels.cuh): one butterfly per thread, 1024-element tiles of 512 threads or 512-element tiles of 256

@@ -154,6 +154,89 @@ __host__ __device__ __forceinline__ void tile_thread_coords(uint32_t tid, uint32
   }
 }
 
+// ---- the tile's own twiddles ---------------------------------------------------------------------------------------------
+// Group g does the levels q = qhi and qhi - 1 (qhi = LOG_R - 1 - 2 g), two butterflies b = 2 lv + pr each; level q multiplies by
+// w_R^((i mod 2^q) * 2^(LOG_R - 1 - q)), an entry of a.wR (R / 2 pairs).  Which of the four products exist is known at compile time.
+template <int LOG_R, int g>
+__host__ __device__ constexpr bool tile_tw_needed(int b) {
+  constexpr int beta = (LOG_R - 2 * (g + 1)) > 0 ? (LOG_R - 2 * (g + 1)) : 0;
+  constexpr int qhi = LOG_R - 1 - 2 * g;
+  const int q = qhi - (b >> 1), pr = b & 1;
+  if (q <= 0) return false;                        // level absent, or twiddle 1
+  const int lb = q - beta;
+  const int hl = lb == 1 ? pr : 2 * pr;
+  if (q == 1 && beta == 0) return (hl & 1) != 0;   // 1 or w^(R/4)
+  return true;
+}
+// index into a.wR of butterfly b's twiddle for the thread whose row base is ibase
+template <int LOG_R, int g>
+__host__ __device__ constexpr uint32_t tile_tw_exponent(int b, uint32_t ibase) {
+  constexpr int beta = (LOG_R - 2 * (g + 1)) > 0 ? (LOG_R - 2 * (g + 1)) : 0;
+  constexpr int qhi = LOG_R - 1 - 2 * g;
+  const int q = qhi - (b >> 1), pr = b & 1;
+  const int lb = q - beta;
+  const int hl = lb == 1 ? pr : 2 * pr;
+  if (q == 1 && beta == 0) return (1u << LOG_R) / 4;  // w^(R/4), the 4th root of unity
+  const uint32_t il = ibase | ((uint32_t)hl << beta);
+  return (il & ((1u << q) - 1u)) << (LOG_R - 1 - q);
+}
+
+// TWIDDLES IN LDS.  Every thread of a tile needs up to 13 of the R / 2 pairs, and which ones depends on its row base alone: read
+// from global memory that is 4 global_load_dwordx4 per pair and thread for a table of 32 R bytes that never leaves the L1.  Cells
+// with room for it copy the table into LDS behind the tile image once per tile (1 or 2 loads per thread, one workgroup barrier in
+// front of the first product; read-only afterwards, so the barrier-free exchanges of the image are untouched) and take the pairs
+// from there: four ds_read_b128 that wait on lgkmcnt and leave vmcnt to the elements and the inter-pass twiddles.
+// A cell qualifies when image + table, times the workgroups per CU its thread count allows, still fit the 160 KiB of a CU -- the
+// table must never cost a workgroup -- and the radix is at most 2^9 (the 2^10 and 2^11 tables do not fit beside any tile that
+// leaves two workgroups per CU).  Workgroups per CU: at 5 waves per SIMD (20 per CU), which a kernel of at most 96 registers may
+// run, the 512- and 1024-element tiles fill the CU with images alone (10 x 16 KiB, 5 x 32 KiB) and no table fits: the radices
+// below 2^8 are counted that way and keep the global loads on those tiles.  Radix 2^8 and 2^9 are counted at 4 waves per SIMD
+// (16 per CU).  That matters for <8,2,*> alone (4 x 40 KiB) and rests on its 98 and 100 registers; on the 2048- and 4096-element
+// tiles 16 and 20 waves are the same 2 and 1 workgroups (<8,3,true> and <8,4,true> do fit 96 registers).  The compiler's register
+// count is not visible here, so tests/native/ntt_occupancy.hip asks the runtime: with and without the table, every qualifying cell.
+// SHK_TW_LDS=0: every cell reads global memory.
+#ifndef SHK_TW_LDS
+#define SHK_TW_LDS 1
+#endif
+template <int LOG_R, int LOG_T>
+__host__ __device__ constexpr bool tile_tw_in_lds() {
+  constexpr int TILE_LOG = LOG_R + LOG_T;
+  if (!SHK_TW_LDS || LOG_R > 9 || TILE_LOG < 8 || TILE_LOG > 12) return false;
+  constexpr long wgs = (LOG_R >= 8 ? 16 : 20) >> (TILE_LOG - 8);  // 2^(TILE_LOG - 8) waves each
+  return ((32L << TILE_LOG) + (32L << LOG_R)) * wgs <= 160L * 1024;
+}
+// bytes of dynamic LDS of a cell
+template <int LOG_R, int LOG_T>
+__host__ __device__ constexpr size_t tile_lds_bytes() {
+  return ((size_t)32 << (LOG_R + LOG_T)) + (tile_tw_in_lds<LOG_R, LOG_T>() ? (size_t)32 << LOG_R : 0);
+}
+// Where 16-byte chunk c (0..3) of the pair with exponent ex lives in the table region, in uint4 units.  A pair is 64 bytes = 16 of
+// the 64 banks, and one ds_read_b128 serves 16 lanes at a time, each lane 4 banks wide: it is conflict-free when the distinct
+// pairs of those 16 lanes differ in the 4-bit key (pair slot mod 4, chunk rotation).  A level reads exponents a power-of-two
+// stride apart (at most 4 distinct per 16 lanes in the column mapping, 16 consecutive or every second one in the row pass's first
+// group, and with bits 0 and 4 or 0, 1 and 5 apart where wave or level bits split a thread's row index), so the key is
+// ex ^ (ex >> 3) ^ (ex >> 4): no XOR of two exponents that one lane group reads together, in any cell, folds to zero.  The key's
+// low half moves the pair inside its aligned group of four, its high half rotates the chunks inside the pair.  A bijection of
+// [0, R/2) x [0, 4) onto [0, 2 R) for every R >= 4; tests/native/tw_lds_map_host.cpp enumerates it.
+__host__ __device__ constexpr uint32_t tw_lds_key(uint32_t ex) { return (ex ^ (ex >> 3) ^ (ex >> 4)) & 15u; }
+__host__ __device__ constexpr uint32_t tw_lds_slot(uint32_t ex, uint32_t c) {
+  const uint32_t k = tw_lds_key(ex);
+  return ((((ex & ~3u) | (k & 3u)) << 2) | (c ^ (k >> 2)));
+}
+// the copy: thread tid of `threads` moves the chunks j = tid, tid + threads, ... < 2 R of a.wR (chunk j = pair j / 4, part j % 4)
+template <int LOG_R, int LOG_T>
+__host__ __device__ constexpr int tile_tw_fill_chunks() {  // steps per thread (rounded up)
+  constexpr int chunks = 2 << LOG_R, threads = 1 << (LOG_R + LOG_T - 2);
+  return (chunks + threads - 1) / threads;
+}
+// the chunk thread tid moves in step k, or -1 (the bound is checked at run time only in a step that not every thread takes)
+template <int LOG_R, int LOG_T>
+__host__ __device__ constexpr int tile_tw_fill_chunk(uint32_t tid, int k) {
+  constexpr uint32_t chunks = 2u << LOG_R, threads = 1u << (LOG_R + LOG_T - 2);
+  const uint32_t j = tid + (uint32_t)k * threads;
+  return ((uint32_t)(k + 1) * threads <= chunks || j < chunks) ? (int)j : -1;
+}
+
 // Register group g: fetch 4 elements (global memory for g == 0, LDS otherwise), do its butterfly levels,
 // and hand the elements to the next group through LDS.
 template <int LOG_R, int LOG_T, bool LAST, int g>
@@ -201,28 +284,53 @@ __device__ __forceinline__ void ntt_group(const NttPassArgs& a, uint4* lds, Tile
 
   // ---- the twiddles of this group's (up to) four butterflies b = 2 lv + pr: which exist is known at compile time ---------
   constexpr int qhi = LOG_R - 1 - 2 * g;
-  auto tw_needed = [](int b) constexpr {
-    const int q = qhi - (b >> 1), pr = b & 1;
-    if (q <= 0) return false;                        // level absent, or twiddle 1
-    const int lb = q - beta;
-    const int hl = lb == 1 ? pr : 2 * pr;
-    if (q == 1 && beta == 0) return (hl & 1) != 0;   // 1 or w^(R/4)
-    return true;
-  };
+  constexpr bool TWL = tile_tw_in_lds<LOG_R, LOG_T>();
+  auto tw_needed = [](int b) constexpr { return tile_tw_needed<LOG_R, g>(b); };
   auto tw_load = [&](int b) {
-    const int q = qhi - (b >> 1), pr = b & 1;
-    const int lb = q - beta;
-    const int hl = lb == 1 ? pr : 2 * pr;
-    if (q == 1 && beta == 0) return fp2_load(a.wR + (R / 4));  // w^(R/4), the 4th root of unity
-    const uint32_t il = th.ibase | ((uint32_t)hl << beta);
-    const uint32_t ex = (il & ((1u << q) - 1u)) << (LOG_R - 1 - q);
-    return fp2_load(a.wR + ex);
+    const uint32_t ex = tile_tw_exponent<LOG_R, g>(b, th.ibase);
+    if constexpr (TWL) {
+      const uint4* tw = lds + (2u << (LOG_R + LOG_T));  // the table region behind the tile image
+      const uint32_t o = tw_lds_slot(ex, 0);            // the other chunks: one XOR each (tw_lds_slot(ex, c) == o ^ c)
+      const uint4 c0 = tw[o], c1 = tw[o ^ 1u], c2 = tw[o ^ 2u], c3 = tw[o ^ 3u];
+      fp2 r;
+      r.w.v[0] = c0.x; r.w.v[1] = c0.y; r.w.v[2] = c0.z; r.w.v[3] = c0.w;
+      r.w.v[4] = c1.x; r.w.v[5] = c1.y; r.w.v[6] = c1.z; r.w.v[7] = c1.w;
+      r.w128.v[0] = c2.x; r.w128.v[1] = c2.y; r.w128.v[2] = c2.z; r.w128.v[3] = c2.w;
+      r.w128.v[4] = c3.x; r.w128.v[5] = c3.y; r.w128.v[6] = c3.z; r.w128.v[7] = c3.w;
+      return r;
+    } else {
+      return fp2_load(a.wR + ex);
+    }
   };
   // one twiddle is always in flight: the first is requested before the elements are fetched, the next before the current
   // product (the product's inline asm keeps the compiler from moving loads across it, so source order is issue order)
   constexpr int first_tw = tw_needed(0) ? 0 : tw_needed(1) ? 1 : tw_needed(2) ? 2 : tw_needed(3) ? 3 : 4;
   fp2 tw_cur, tw_nxt;
-  if constexpr (first_tw < 4) tw_cur = tw_load(first_tw);
+  // Twiddles in LDS, first group: this thread's share of the table is requested first and the elements right behind it, so that
+  // the copy waits for the table alone (vmcnt counts in order) while the elements are in flight; the workgroup barrier and the
+  // first twiddle read follow the element loads (tw_fill_finish), in front of the group's first product.
+  constexpr int FILL = tile_tw_fill_chunks<LOG_R, LOG_T>();  // 1 or 2 in every qualifying cell (LOG_T >= 2)
+  static_assert(!TWL || FILL == 1 || FILL == 2, "twiddle copy: one or two chunks per thread");
+  uint4 tw_fill0 = make_uint4(0, 0, 0, 0), tw_fill1 = tw_fill0;
+  if constexpr (TWL && g == 0) {
+    const uint4* src = reinterpret_cast<const uint4*>(a.wR);
+    const int j0 = tile_tw_fill_chunk<LOG_R, LOG_T>(tid, 0), j1 = tile_tw_fill_chunk<LOG_R, LOG_T>(tid, 1);
+    tw_fill0 = src[j0 < 0 ? 0 : j0];
+    if constexpr (FILL == 2) tw_fill1 = src[j1 < 0 ? 0 : j1];
+    // no instruction of its own: keeps the compiler from sinking the requests to the copy below, behind the element loads
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "singlethread");
+  }
+  auto tw_fill_finish = [&]() {
+    uint4* tw = lds + (2u << (LOG_R + LOG_T));
+    const int j0 = tile_tw_fill_chunk<LOG_R, LOG_T>(tid, 0), j1 = tile_tw_fill_chunk<LOG_R, LOG_T>(tid, 1);
+    if (j0 >= 0) tw[tw_lds_slot((uint32_t)j0 >> 2, (uint32_t)j0 & 3u)] = tw_fill0;
+    if constexpr (FILL == 2) {
+      if (j1 >= 0) tw[tw_lds_slot((uint32_t)j1 >> 2, (uint32_t)j1 & 3u)] = tw_fill1;
+    }
+    __syncthreads();
+    if constexpr (first_tw < 4) tw_cur = tw_load(first_tw);
+  };
+  if constexpr (first_tw < 4 && !(TWL && g == 0)) tw_cur = tw_load(first_tw);
 
   // ---- zero-padded source whose non-zero part ends inside the first quarter of the rows (the 8x low-degree extension:
   // rows i >= R / 8 of every column are zero): this thread's elements 1..3 are zero, so the group's two levels are
@@ -234,8 +342,13 @@ __device__ __forceinline__ void ntt_group(const NttPassArgs& a, uint4* lds, Tile
       const uint64_t off = ((uint64_t)th.ibase << a.log_S) + th.j2;  // element h = 0
       const bool in = off < a.src_n;
       th.x[0] = th.x[1] = th.x[2] = th.x[3] = fp_zero();
+      fp x0 = fp_zero();
+      if constexpr (TWL) {
+        if (FP_ANY(in)) x0 = fp_load(a.src + th.sbase + (in ? off : 0));
+        tw_fill_finish();  // src_n is the launch's: every thread of the workgroup comes this way
+      }
       if (FP_ANY(in)) {  // wave-uniform
-        fp x0 = fp_load(a.src + th.sbase + (in ? off : 0));
+        if constexpr (!TWL) x0 = fp_load(a.src + th.sbase + (in ? off : 0));
         const fp2 tw_b = tw_load(2), tw_c = tw_load(3);  // tw_cur holds butterfly 0's
 #pragma unroll
         for (int w = 0; w < 8; ++w) x0.v[w] = in ? x0.v[w] : 0u;
@@ -262,12 +375,15 @@ __device__ __forceinline__ void ntt_group(const NttPassArgs& a, uint4* lds, Tile
         for (int w = 0; w < 8; ++w) v.v[w] = in ? v.v[w] : 0u;
         th.x[h] = v;
       }
+      if constexpr (TWL) tw_fill_finish();
     } else {
 #pragma unroll
       for (int h = 0; h < 4; ++h) {
         const uint32_t i = th.ibase | ((uint32_t)h << beta);
         th.x[h] = LAST ? fp_load(a.src + th.gbase + i) : fp_load(a.src + th.gbase + ((uint64_t)i << a.log_S));
       }
+      // in the block of the element loads: the copy's wait then counts exactly these eight requests behind the table's
+      if constexpr (TWL) tw_fill_finish();
     }
   } else {
 #pragma unroll
