@@ -57,6 +57,17 @@ def prove_mimc_batch(unit_ids, steps, ext=8, samples=40, chunk=16):
     return out
 
 
+def verify_fri_batch(proofs, merkle_roots, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0, samples=40, modulus=MIMC_P):
+    """The flat FRI proofs of one shape (a list of bytes, e.g. the second items of prove_mimc_batch's pairs) and their committed roots,
+    verified on this process's GPU in one call: sh_fri_verify_batch over the MiMC prime, sh_mod_fri_verify_batch over any other odd
+    modulus below 2^256.  -> [bool] per proof."""
+    from . import fri
+    flats, roots = b"".join(proofs), b"".join(merkle_roots)
+    if int(modulus) == MIMC_P:
+        return fri.verify_flat_batch(flats, roots, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of, len(proofs), samples)
+    return fri.mod_verify_flat_batch(modulus, flats, roots, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of, len(proofs), samples)
+
+
 def mimc_stark_unit(j, steps, constant=42):
     """Unit j of the synthetic many-proof workload as a full STARK: the reference's MiMC formulation of
     test_stark.py:265-293 -- width 2, step polynomials [X_1, X_1 + X_2^3], i.e. x <- x^3 + k with the round constant k

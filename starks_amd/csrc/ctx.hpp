@@ -223,6 +223,11 @@ int mod_table(sh_ctx* c, const ModCall& mc, const fpm** out);
 int mod_run(sh_ctx* c, const ModCall& mc, const fpm* tw, const void* src, uint64_t n_in, void* dst, uint32_t batch, bool wire_in,
             bool wire_out);
 
+// ---- modverify.hip --------------------------------------------------------------------------------------
+// the host verifier behind sh_mod_fri_verify: serial, no context, no GPU
+int mod_fri_verify(const uint8_t modulus[32], const uint8_t* proof, uint64_t proof_len, const uint8_t merkle_root[32], uint64_t n,
+                   const uint8_t root[32], uint64_t maxdeg_plus_1, uint32_t exclude_multiples_of, uint32_t samples);
+
 // ---- api_stark.hip --------------------------------------------------------------------------------------
 // Device layout of the step-polynomial description (one allocation, ctx->terms_dev)
 struct TermLayout {

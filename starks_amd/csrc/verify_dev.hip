@@ -159,12 +159,9 @@ __global__ void __launch_bounds__(VB_TPB) vb_final_kernel(const uint8_t* proofs,
 
 }  // namespace
 
-// Launch the whole verification of `batch` proofs of plan p.  ys / flags: device scratch of batch * p.ys_per_proof and batch u32
-// (flags zeroed here).  STARK only: inputs / outputs limb form (element (b, d) at (b width + d) io_stride), coef / exps / tbegin = the
-// step polynomials (exponent rows of `row` bytes).  FRI only: roots [batch][32] = the committed roots.
-hipError_t shk_verify_batch(const VbPlan& p, const uint8_t* proofs, uint32_t batch, const uint8_t* roots, const fp* inputs,
-                            const fp* outputs, uint64_t io_stride, const fp* coef, const uint8_t* exps, uint32_t row,
-                            const uint32_t* tbegin, uint32_t* ys, uint32_t* flags, int32_t* status, hipStream_t st) {
+// launches 1 and 2 above (declared in verify_items.cuh)
+hipError_t shk_verify_sets_and_branches(const VbPlan& p, const uint8_t* proofs, uint32_t batch, const uint8_t* roots, uint32_t* ys,
+                                        uint32_t* flags, hipStream_t st) {
   hipError_t e = hipMemsetAsync(flags, 0, (size_t)batch * 4, st);
   if (e != hipSuccess) return e;
   const uint64_t plen = p.plen;
@@ -218,6 +215,18 @@ hipError_t shk_verify_batch(const VbPlan& p, const uint8_t* proofs, uint32_t bat
                        cs, ys, p.ys_per_proof, flags);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
+  return hipSuccess;
+}
+
+// Launch the whole verification of `batch` proofs of plan p.  ys / flags: device scratch of batch * p.ys_per_proof and batch u32
+// (flags zeroed here).  STARK only: inputs / outputs limb form (element (b, d) at (b width + d) io_stride), coef / exps / tbegin = the
+// step polynomials (exponent rows of `row` bytes).  FRI only: roots [batch][32] = the committed roots.
+hipError_t shk_verify_batch(const VbPlan& p, const uint8_t* proofs, uint32_t batch, const uint8_t* roots, const fp* inputs,
+                            const fp* outputs, uint64_t io_stride, const fp* coef, const uint8_t* exps, uint32_t row,
+                            const uint32_t* tbegin, uint32_t* ys, uint32_t* flags, int32_t* status, hipStream_t st) {
+  hipError_t e = shk_verify_sets_and_branches(p, proofs, batch, roots, ys, flags, st);
+  if (e != hipSuccess) return e;
+  const uint64_t plen = p.plen;
   // 3. FRI rows
   if (p.rounds) {
     VbRowsArgs ra;

@@ -340,3 +340,8 @@ inline int vb_plan_stark_proof(VbPlan* p, uint64_t steps, uint32_t ext, uint32_t
   p->stark = 1;
   return rc;
 }
+
+// verify_dev.hip: the field-free head of a batch verification -- zero the flags, draw every index set, check every Merkle branch.  It
+// reads the plan's offsets and counts alone; the verifier over another modulus (modverify_dev.hip) starts with it too.
+hipError_t shk_verify_sets_and_branches(const VbPlan& p, const uint8_t* proofs, uint32_t batch, const uint8_t* roots, uint32_t* ys,
+                                        uint32_t* flags, hipStream_t st);

@@ -9,6 +9,7 @@ proof back and `unpack_proof` rebuilds the reference's nested lists.
                                                       exclude_multiples_of=0, fri_spot_check_security_factor=40)
     prove_low_degree(...)  -- the upstream name of the same function (test_fri.py:170)
     SmoothSubgroupFRI(field).verify_proximity_proof(...) -- host-side verifier (fri.py:268-366)
+    verify_flat / verify_flat_batch, mod_verify_flat / mod_verify_flat_batch -- the library's C and GPU verifiers on flat proofs
 """
 import ctypes
 
@@ -129,7 +130,7 @@ def _interp4_eval(xs, ys, x, p):
             if l != k:
                 num = num * (x - xs[l]) % p
                 den = den * (xs[k] - xs[l]) % p
-        total = (total + num * pow(den, p - 2, p)) % p
+        total = (total + num * pow(den, -1, p)) % p
     return total
 
 
@@ -144,7 +145,7 @@ def _lagrange_eval_all(xs, ys, pts, p):
                 if l != k:
                     num = num * (x - xs[l]) % p
                     den = den * (xs[k] - xs[l]) % p
-            total = (total + num * pow(den, p - 2, p)) % p
+            total = (total + num * pow(den, -1, p)) % p
         out.append(total)
     return out
 
@@ -215,6 +216,32 @@ def verify_flat_batch(flats, merkle_roots, n, root_of_unity, maxdeg_plus_1, excl
     return [s == 0 for s in status]
 
 
+def mod_verify_flat(modulus, flat, merkle_root, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0, samples=40):
+    """verify_flat over any odd modulus below 2^256 (sh_mod_fri_verify: host C++, no GPU) on a flat proof as mod_prove_flat returns it;
+    merkle_root = node 1 of the tree over the evaluations.  Composite moduli are decided correctly (no Fermat inversion).  True /
+    AssertionError like the reference's verifier."""
+    rc = _lib.lib().sh_mod_fri_verify(int(modulus).to_bytes(32, "big"), bytes(flat), len(flat), bytes(merkle_root), n,
+                                      int(root_of_unity).to_bytes(32, "big"), maxdeg_plus_1, exclude_multiples_of, samples)
+    if rc == -9:
+        raise AssertionError("FRI proof rejected")
+    _lib.check(rc, "sh_mod_fri_verify")
+    return True
+
+
+def mod_verify_flat_batch(modulus, flats, merkle_roots, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0, batch=1, samples=40):
+    """verify_flat_batch over any odd modulus below 2^256 (sh_mod_fri_verify_batch): `batch` flat proofs of one shape back to back and
+    their 32-byte committed roots -> [bool] per proof, each the decision mod_verify_flat takes on that proof alone."""
+    flats = bytes(flats)
+    if batch < 1 or len(flats) % batch:
+        raise ValueError("flats must hold batch proofs of equal length")
+    status = (ctypes.c_int32 * batch)()
+    rc = _lib.lib().sh_mod_fri_verify_batch(_lib.ctx(), int(modulus).to_bytes(32, "big"), flats, len(flats) // batch, bytes(merkle_roots), n,
+                                            int(root_of_unity).to_bytes(32, "big"), maxdeg_plus_1, exclude_multiples_of, samples, batch,
+                                            status)
+    _lib.check(rc, "sh_mod_fri_verify_batch")  # a shape error, or a proof length that is not the shape's
+    return [s == 0 for s in status]
+
+
 class SmoothSubgroupFRI(object):
     """fri.py:176-366 (class name and method signatures of the reference's commented-out driver)."""
 
@@ -234,14 +261,21 @@ class SmoothSubgroupFRI(object):
 
     def verify_proximity_proof_native(self, proof, merkle_root, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0,
                                       fri_spot_check_security_factor=40):
-        """The same decision from the library's C verifier (sh_fri_verify) on the packed proof: milliseconds where the Python
-        verifier above takes tenths of a second.  (verify_proximity_proof stays the line-by-line mirror of the reference: it
-        shares no arithmetic with the device code, which is what the parity tests want from a checker.)"""
-        n = _lib.order_of_root(root_of_unity)
+        """The same decision from the library's C verifier on the packed proof (sh_fri_verify over the MiMC prime, sh_mod_fri_verify
+        over any other odd modulus below 2^256): milliseconds where the Python verifier above takes tenths of a second.
+        (verify_proximity_proof stays the line-by-line mirror of the reference: it shares no arithmetic with the device code, which
+        is what the parity tests want from a checker.)"""
+        p = int(self.field.p)
+        if p != MIMC_P and (p < 3 or p % 2 == 0 or p >> 256):
+            raise NotImplementedError("starks_amd accelerates odd moduli below 2^256 only")
+        n = _lib.order_of_root(root_of_unity, p)
         if n is None:
             raise NotImplementedError("root_of_unity must have power-of-two order")
-        return verify_flat(pack_proof(proof), merkle_root, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of,
-                           fri_spot_check_security_factor)
+        if p == MIMC_P:
+            return verify_flat(pack_proof(proof), merkle_root, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of,
+                               fri_spot_check_security_factor)
+        return mod_verify_flat(p, pack_proof(proof), merkle_root, n, int(root_of_unity) % p, maxdeg_plus_1, exclude_multiples_of,
+                               fri_spot_check_security_factor)
 
 
 FRI = SmoothSubgroupFRI  # the name starks/stark.py:13 tries to import
