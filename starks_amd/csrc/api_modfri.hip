@@ -45,12 +45,21 @@ int modfri_run(sh_ctx* c, const ModCall& mc, const void* src, bool wire_in, uint
   SH_TRY(mod_table(c, mc, &tw));
   FriBuffers fb;  // the MiMC commit's arenas: an element is 32 bytes there and here
   SH_TRY(fri_buffers(c, n, batch, samples, &fb));
+  // values = fft(f) over the whole domain (fri.py:207-208): plain, canonical
+  SH_TRY(mod_run(c, mc, tw, src, n_coeffs, fb.vals, batch, wire_in, false));
+  return modfri_rounds(c, mc, tw, fb, n, maxdeg_plus_1, exclude, samples, batch, d_proof, fri_proof_len(n, maxdeg_plus_1, samples), false);
+}
+}  // namespace
+
+namespace shk {
+// The rounds of the commit (fri.py:212-266) on the plain canonical evaluations in fb.vals (and, when have_tree, their Merkle tree in
+// fb.tree: the generic STARK prover has built it for its spot checks); proof b is written at d_proof + b * stride.
+int modfri_rounds(sh_ctx* c, const ModCall& mc, const fpm* tw, FriBuffers fb, uint64_t n, uint64_t maxdeg_plus_1, uint32_t exclude,
+                  uint32_t samples, uint32_t batch, uint8_t* d_proof, uint64_t stride, bool have_tree) {
   fpm* vals = reinterpret_cast<fpm*>(fb.vals);
   fpm* next = reinterpret_cast<fpm*>(fb.next);
   uint32_t* tree = fb.tree;
   uint32_t* tree2 = fb.tree2;
-  // values = fft(f) over the whole domain (fri.py:207-208): plain, canonical
-  SH_TRY(mod_run(c, mc, tw, src, n_coeffs, vals, batch, wire_in, false));
   MfFold fa = n >= 4 ? fold_args(mc, tw, n) : MfFold{};
   fa.batch = batch;
   FriSampleArgs sa;  // what the sampler reads
@@ -63,12 +72,12 @@ int modfri_run(sh_ctx* c, const ModCall& mc, const void* src, bool wire_in, uint
   ga.batch = batch;
   ga.ys = fb.ys;
   ga.proof = d_proof;
-  ga.proof_stride = fri_proof_len(n, maxdeg_plus_1, samples);
+  ga.proof_stride = stride;
   uint64_t nn = n, md = maxdeg_plus_1, off = 0;
   uint32_t round = 0, ys_off = 0;
   while (md > 16) {  // at most SHK_FRI_MAX_ROUNDS rounds of at least 16 points: fri_validate has refused anything else
     const uint32_t s = round == 0 ? samples : 40;
-    if (round == 0) {  // m = merkelize(values), fri.py:224; a later round's m is the round before's m2
+    if (round == 0 && !have_tree) {  // m = merkelize(values), fri.py:224; a later round's m is the round before's m2
       MfTree t = {vals, tree, nn, batch, 0};
       HIP_TRY(c, shk_mf_leaves(t, c->stream));
       HIP_TRY(c, shk_merkle_upper_levels(nn, batch, tree, c->stream));
@@ -118,7 +127,7 @@ int modfri_run(sh_ctx* c, const ModCall& mc, const void* src, bool wire_in, uint
   HIP_TRY(c, shk_mf_gather(ga, c->stream));       // fri.py:251-254 and the final layer
   return SH_OK;
 }
-}  // namespace
+}  // namespace shk
 
 extern "C" {
 

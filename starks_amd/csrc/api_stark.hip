@@ -61,9 +61,7 @@ int stark_terms(sh_ctx* c, uint32_t width, const uint8_t* coefs, const uint8_t* 
   c->terms_key.swap(key);
   return SH_OK;
 }
-}  // namespace shk
 
-namespace {
 uint64_t stark_header_len(uint64_t n, uint32_t width, uint32_t samples) {
   const uint64_t lg = (uint64_t)ilog2(n), k = 3ull * width;
   return 64 + (uint64_t)samples * 32 * (2 * (2 * k + (lg - 1)) + (lg + 1));
@@ -96,6 +94,9 @@ int bad_flags(sh_ctx* c, uint32_t batch) {
   c->bad_cap = cap;
   return SH_OK;
 }
+}  // namespace shk
+
+namespace {
 
 int run_stark(sh_ctx* c, fp* d_wit, const fp* d_inputs, uint64_t steps, uint32_t ext, uint32_t width, uint32_t samples,
               uint32_t batch, uint8_t* d_proof) {

@@ -84,6 +84,10 @@ struct sh_ctx {
   void* terms_dev = nullptr;   // [terms][derivative terms]: see TermLayout
   uint32_t terms_begin[SHK_STARK_MAX_WIDTH + 1] = {};
   uint32_t terms_degree = 0;
+  // the generic prover's term image (api_modstark.hip), beside the MiMC path's: keyed by modulus plus term bytes
+  std::vector<uint8_t> mod_terms_key;
+  void* mod_terms_dev = nullptr;  // ModTermLayout
+  uint32_t mod_terms_begin[SHK_STARK_MAX_WIDTH + 1] = {};
   uint32_t* bad_flag = nullptr;  // [bad_cap] per-proof constraint flags of the calls since the last sh_stark_status*
   uint32_t bad_cap = 0;
 };
@@ -223,6 +227,12 @@ int mod_table(sh_ctx* c, const ModCall& mc, const fpm** out);
 int mod_run(sh_ctx* c, const ModCall& mc, const fpm* tw, const void* src, uint64_t n_in, void* dst, uint32_t batch, bool wire_in,
             bool wire_out);
 
+// ---- api_modfri.hip -------------------------------------------------------------------------------------
+// the commit rounds over mc's modulus on the evaluations in fb.vals (tw = mod_table of the n-point forward transform); with have_tree
+// the tree of round 0 is already in fb.tree.  The FRI-only entries pass have_tree = false and stride = fri_proof_len.
+int modfri_rounds(sh_ctx* c, const ModCall& mc, const fpm* tw, FriBuffers fb, uint64_t n, uint64_t maxdeg_plus_1, uint32_t exclude,
+                  uint32_t samples, uint32_t batch, uint8_t* d_proof, uint64_t stride, bool have_tree);
+
 // ---- modverify.hip --------------------------------------------------------------------------------------
 // the host verifier behind sh_mod_fri_verify: serial, no context, no GPU
 int mod_fri_verify(const uint8_t modulus[32], const uint8_t* proof, uint64_t proof_len, const uint8_t merkle_root[32], uint64_t n,
@@ -241,5 +251,9 @@ struct TermLayout {
   static constexpr size_t total = dbegin + 4 * (SHK_STARK_MAX_WIDTH * SHK_STARK_MAX_WIDTH + 1);
 };
 int stark_terms(sh_ctx* c, uint32_t width, const uint8_t* coefs, const uint8_t* exps, const uint32_t* counts);
+// the flat proof's bytes before the FRI part; the shape rule of both provers (degree = the step polynomials'); the per-proof flags
+uint64_t stark_header_len(uint64_t n, uint32_t width, uint32_t samples);
+int stark_check_shape(uint64_t steps, uint32_t ext, uint32_t width, uint32_t degree, uint32_t samples);
+int bad_flags(sh_ctx* c, uint32_t batch);
 
 }  // namespace shk

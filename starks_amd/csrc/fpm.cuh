@@ -20,7 +20,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#ifndef FPM_HD  // a host program that walks many instantiations may define it without the inlining
 #define FPM_HD __host__ __device__ __forceinline__
+#endif
 
 struct fpm {
   uint32_t v[8];

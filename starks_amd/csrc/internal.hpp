@@ -233,6 +233,26 @@ hipError_t shk_mf_leaves(const MfTree& t, hipStream_t st);
 hipError_t shk_mf_fold(const MfFold& a, const fpm_mod& M, hipStream_t st);
 hipError_t shk_mf_gather(const MfGather& a, hipStream_t st);
 
+// ---- modstark.hip: the STARK prover's middle over any prime modulus below 2^256 (stark.py:233-279; modstark_items.cuh, which the two
+// files that use these include themselves) ---------------------------------------------------------------------------------------------
+struct MsArgs;
+struct MsInv;
+struct MsTables;
+struct MsGather;
+// a.out[i] = a.in[i]^-1, Montgomery form in and out, 0 for 0
+hipError_t shk_ms_batch_inv(const MsInv& a, const fpm_mod& M, hipStream_t st);
+// t.table = inv_z2 | fz | xpow of (p, steps, ext); t.den is [2][n] of scratch; pm2 = p - 2
+hipError_t shk_ms_tables(const MsTables& t, const fpm& pm2, const fpm_mod& M, hipStream_t st);
+hipError_t shk_ms_interp(const MsArgs& a, const fpm_mod& M, hipStream_t st);
+hipError_t shk_ms_qprep(const fpm* pcoef, fpm* q, uint64_t steps, uint64_t cols, const fpm_mod& M, hipStream_t st);
+// D = C / Z and B = (P - I) / Z2 on the whole domain, then the packed-leaf Merkle tree over (P, D, B)
+hipError_t shk_ms_quotients_and_merkelize(const MsArgs& a, const fpm_mod& M, uint32_t* d_nodes, hipStream_t st);
+// d_scal [batch][width][3]: alpha_j, alpha_j beta, alpha_j gamma in Montgomery form
+hipError_t shk_ms_scalars(const uint32_t* d_mnodes, uint64_t tree_words, uint32_t width, uint32_t batch, const fpm& cpow, fpm* d_scal,
+                          const fpm_mod& M, hipStream_t st);
+hipError_t shk_ms_lincomb(const MsArgs& a, const fpm* d_scal, fpm* d_l, const fpm_mod& M, hipStream_t st);
+hipError_t shk_ms_gather(const MsArgs& a, const MsGather& ga, hipStream_t st);
+
 // ---- ntt64.hip: the transform over any odd modulus below 2^64 on packed 64-bit words (ntt64_items.cuh) ------------------------------
 #include "ntt64_items.cuh"
 // one tile pass of the plan (n64_pass); the modulus block is an argument of the launch

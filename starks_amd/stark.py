@@ -4,7 +4,8 @@
     proof = stark.mk_proof(witness, boundary)          # [m_root, l_root, branches, fri_proof]
     assert stark.verify_proof(proof, witness, boundary)
 
-`mk_proof` is one call into libstarkhip.so (sh_stark_prove, csrc/api_stark.hip:run_stark): low-degree extension, the
+`mk_proof` is one call into libstarkhip.so (sh_stark_prove, csrc/api_stark.hip:run_stark; over a field other than the MiMC prime's
+sh_mod_stark_prove, csrc/api_modstark.hip, for any odd prime below 2^256 over which 7^((p - 1) // (steps * ext)) has full order): low-degree extension, the
 constraint quotient D and boundary quotient B, the packed Merkle tree, the pseudorandom linear combination, the spot
 checks and the FRI commit all run on the device and one copy brings the flat proof back.  The reference builds D and B
 with O(n^2) coefficient arithmetic (stark.py:38-104); the device computes the same polynomials through the evaluation
@@ -116,6 +117,42 @@ def prove_flat(witness_bytes, input_bytes, steps, ext, width, step_polys, batch=
     return out.raw
 
 
+def mod_prove_flat(modulus, witness_bytes, input_bytes, steps, ext, width, step_polys, batch=1, samples=SPOT_CHECKS):
+    """prove_flat over any prime modulus below 2^256 (sh_mod_stark_prove): the same arguments and the same flat layout and length; any
+    256-bit witness, input or coefficient value is taken modulo `modulus`.  G2 = 7^((p - 1) // (steps * ext)) must have order steps * ext."""
+    if len(witness_bytes) != 32 * batch * width * steps or len(input_bytes) != 32 * batch * width:
+        raise ValueError("witness must hold batch*width*steps and inputs batch*width 32-byte elements "
+                         "(got %d and %d bytes for batch=%d, width=%d, steps=%d)"
+                         % (len(witness_bytes), len(input_bytes), batch, width, steps))
+    coefs, exps, counts, degree = pack_step_polys(step_polys, width, p=modulus)
+    plen = proof_len(steps, ext, width, degree, samples)
+    if plen == 0:
+        raise NotImplementedError("starks_amd.STARK: unsupported shape (steps=%d, ext=%d, width=%d, degree=%d)"
+                                  % (steps, ext, width, degree))
+    out = ctypes.create_string_buffer(plen * batch)
+    rc = _lib.lib().sh_mod_stark_prove(_lib.ctx(), int(modulus).to_bytes(32, "big"), bytes(witness_bytes), bytes(input_bytes), steps, ext,
+                                       width, coefs, exps, counts, samples, batch, out, plen * batch)
+    if rc == -8:  # SH_ERR_CONSTRAINT: the reference's `assert cp % z == 0` (stark.py:76)
+        raise AssertionError("constraint polynomial is not a multiple of Z: the witness is not a valid trace")
+    _lib.check(rc, "sh_mod_stark_prove")
+    return out.raw
+
+
+def unsupported_field_reason(modulus, precision):
+    """None when STARK runs over Z/modulus on a domain of `precision` points (the MiMC prime, or an odd modulus below 2^256 over which
+    the reference's G2 = 7^((p - 1) // precision) has order precision), else the reason it does not."""
+    if modulus == MIMC_P:
+        return None
+    if modulus < 3 or modulus % 2 == 0:
+        return "the modulus %d is even or below 3 (the generic prover takes odd prime moduli)" % modulus
+    if modulus >> 256:
+        return "the modulus is 2^256 or more"
+    if precision < 2 or precision & (precision - 1) or pow(pow(7, (modulus - 1) // precision, modulus), precision // 2, modulus) != modulus - 1:
+        return ("7 is not of full 2-power order: G2 = 7^((p - 1) // %d) does not have order %d modulo %d (7 is a quadratic residue, or "
+                "p - 1 has too few factors of two)" % (precision, precision, modulus))
+    return None
+
+
 def verify_flat(flat, input_bytes, output_bytes, steps, ext, width, step_polys, samples=SPOT_CHECKS):
     """The library's own verifier (sh_stark_verify: host C++ behind the C ABI; the decisions of STARK.verify_proof below) on a FLAT
     proof as prove_flat returns it.  input_bytes / output_bytes: [width] wire-form boundary inputs and witness[dim][-1]."""
@@ -206,9 +243,10 @@ class STARK(object):
         self.extension_factor = extension_factor
         self.precision = steps * extension_factor
         self.spot_check_security_factor = spot_check_security_factor
-        modulus = getattr(field, "p", MIMC_P)
-        if modulus != MIMC_P:
-            raise NotImplementedError("starks_amd.STARK is compiled for the MiMC prime 2^256 - 351*2^32 + 1")
+        modulus = int(getattr(field, "p", MIMC_P))
+        reason = unsupported_field_reason(modulus, self.precision)
+        if reason:  # the MiMC prime runs sh_stark_prove, any other prime with a G2 of full order sh_mod_stark_prove
+            raise NotImplementedError("starks_amd.STARK: " + reason)
         self.modulus = modulus
         self.G2 = field(7) ** ((modulus - 1) // self.precision)   # stark.py:205
         self.G1 = self.G2 ** extension_factor                      # stark.py:208
@@ -224,9 +262,13 @@ class STARK(object):
             raise ValueError("witness must be width x steps")
         if len(boundary) < self.width:
             raise IndexError("boundary must hold one (step, dim, value) constraint per dimension")  # boundary[dim], stark.py:91
-        wb = b"".join(_lib.to_wire(col) for col in witness)
-        ib = _lib.to_wire([constraint[2] for constraint in boundary[:self.width]])
-        flat = prove_flat(wb, ib, self.steps, self.extension_factor, self.width, self.step_polys)
+        p = self.modulus
+        wb = b"".join(_lib.to_wire(col, p) for col in witness)
+        ib = _lib.to_wire([constraint[2] for constraint in boundary[:self.width]], p)
+        if p == MIMC_P:
+            flat = prove_flat(wb, ib, self.steps, self.extension_factor, self.width, self.step_polys)
+        else:
+            flat = mod_prove_flat(p, wb, ib, self.steps, self.extension_factor, self.width, self.step_polys)
         return unpack_proof(flat, self.steps, self.extension_factor, self.width, self.get_degree())
 
     def compute_merkle_spot_checks(self, mtree, l_mtree, samples=80):
@@ -237,7 +279,7 @@ class STARK(object):
         """stark.py:281-316"""
         m_root, l_root, branches, fri_proof = proof
         assert fri.verify_low_degree_proof(fri_proof, l_root, self.G2, self.steps * self.get_degree(),
-                                           exclude_multiples_of=self.extension_factor)
+                                           exclude_multiples_of=self.extension_factor, modulus=self.modulus)
         samples = self.spot_check_security_factor
         positions = get_pseudorandom_indices(l_root, self.precision, samples, exclude_multiples_of=self.extension_factor)
         ks = get_pseudorandom_ks(m_root, 4)
@@ -248,6 +290,9 @@ class STARK(object):
     def verify_proof_native(self, proof, witness, boundary):
         """The same decision from the library's C verifier (sh_stark_verify) on the packed proof -- about 50 times faster than the
         Python verifier above, which stays the line-by-line mirror of the reference (no arithmetic shared with the device code)."""
+        if self.modulus != MIMC_P:
+            raise NotImplementedError("starks_amd.STARK.verify_proof_native: there is no C STARK verifier over another modulus; "
+                                      "verify_proof is the verifier there")
         inputs = _lib.to_wire([constraint[2] for constraint in boundary[:self.width]])
         outputs = _lib.to_wire([col[-1] for col in witness])
         return verify_flat(pack_proof(proof), inputs, outputs, self.steps, self.extension_factor, self.width, self.step_polys,
