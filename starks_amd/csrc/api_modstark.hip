@@ -7,18 +7,6 @@
 using namespace shk;
 
 namespace {
-// Device layout of the step-polynomial description over a run-time modulus (one allocation, ctx->mod_terms_dev): TermLayout's, with
-// Montgomery-form coefficients and exponent rows of `width` bytes
-struct ModTermLayout {
-  static constexpr size_t MAXT = SHK_STARK_MAX_TERMS, MAXD = SHK_STARK_MAX_TERMS * SHK_STARK_MAX_WIDTH;
-  static constexpr size_t coef = 0;                                    // fpm[MAXT]
-  static constexpr size_t dcoef = coef + MAXT * sizeof(fpm);           // fpm[MAXD]
-  static constexpr size_t exps = dcoef + MAXD * sizeof(fpm);           // u8[MAXT][width]
-  static constexpr size_t dexps = exps + MAXT * SHK_STARK_MAX_WIDTH;   // u8[MAXD][width]
-  static constexpr size_t dbegin = (dexps + MAXD * SHK_STARK_MAX_WIDTH + 3) & ~(size_t)3;  // u32[W * W + 1]
-  static constexpr size_t total = dbegin + 4 * (SHK_STARK_MAX_WIDTH * SHK_STARK_MAX_WIDTH + 1);
-};
-
 // everything the host derives from the arguments before a launch
 struct ModStarkCall {
   ModCall fwd_n, inv_s, fwd_s;  // the n-point transform over G2, the steps-point inverse and forward transforms over G1
@@ -72,6 +60,9 @@ int mod_stark_check(sh_ctx* c, const char* who, const uint8_t modulus[32], uint6
   return SH_OK;
 }
 
+}  // namespace
+
+namespace shk {
 // Parse + upload the step polynomials' terms and their partial derivatives over M (skipped when equal to the previous generic call's)
 int mod_stark_terms(sh_ctx* c, const fpm_mod& M, uint32_t width, const uint8_t* coefs, const uint8_t* exps, const uint32_t* counts,
                     uint64_t total) {
@@ -96,7 +87,9 @@ int mod_stark_terms(sh_ctx* c, const fpm_mod& M, uint32_t width, const uint8_t* 
   c->mod_terms_key.swap(key);
   return SH_OK;
 }
+}  // namespace shk
 
+namespace {
 // the domain tables of (p, steps, ext) -- inv_z2 | fz | xpow, 3 n elements shared by every proof --: a plan like any other, in the
 // byte-budgeted cache.  scratch = 2 n elements that nothing queued still reads.
 int mod_stark_tables(sh_ctx* c, const ModStarkCall& sc, const fpm* tw, uint64_t steps, uint32_t ext, const fpm& x_last, fpm* scratch,

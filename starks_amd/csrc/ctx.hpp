@@ -238,6 +238,28 @@ int modfri_rounds(sh_ctx* c, const ModCall& mc, const fpm* tw, FriBuffers fb, ui
 int mod_fri_verify(const uint8_t modulus[32], const uint8_t* proof, uint64_t proof_len, const uint8_t merkle_root[32], uint64_t n,
                    const uint8_t root[32], uint64_t maxdeg_plus_1, uint32_t exclude_multiples_of, uint32_t samples);
 
+// the host verifier behind sh_mod_stark_verify (stark.py:281-388 over IntegersModP(p)): serial, no context, no GPU
+int mod_stark_verify(const uint8_t modulus[32], const uint8_t* proof, uint64_t proof_len, const uint8_t* inputs, const uint8_t* outputs,
+                     uint64_t steps, uint32_t ext, uint32_t width, const uint8_t* term_coefs, const uint8_t* term_exps,
+                     const uint32_t* term_counts, uint32_t samples);
+
+// ---- api_modstark.hip -----------------------------------------------------------------------------------
+// Device layout of the step-polynomial description over a run-time modulus (one allocation, ctx->mod_terms_dev): TermLayout's, with
+// Montgomery-form coefficients and exponent rows of `width` bytes (TermLayout's rows have width + 1)
+struct ModTermLayout {
+  static constexpr size_t MAXT = SHK_STARK_MAX_TERMS, MAXD = SHK_STARK_MAX_TERMS * SHK_STARK_MAX_WIDTH;
+  static constexpr size_t coef = 0;                                    // fpm[MAXT]
+  static constexpr size_t dcoef = coef + MAXT * sizeof(fpm);           // fpm[MAXD]
+  static constexpr size_t exps = dcoef + MAXD * sizeof(fpm);           // u8[MAXT][width]
+  static constexpr size_t dexps = exps + MAXT * SHK_STARK_MAX_WIDTH;   // u8[MAXD][width]
+  static constexpr size_t dbegin = (dexps + MAXD * SHK_STARK_MAX_WIDTH + 3) & ~(size_t)3;  // u32[W * W + 1]
+  static constexpr size_t total = dbegin + 4 * (SHK_STARK_MAX_WIDTH * SHK_STARK_MAX_WIDTH + 1);
+};
+// Parse + upload the step polynomials' terms over M into ctx->mod_terms_dev / mod_terms_begin; skipped when modulus and terms equal
+// the previous generic call's, prover or verifier: a prove -> verify pair over one system uploads once.  total = the sum of counts.
+int mod_stark_terms(sh_ctx* c, const fpm_mod& M, uint32_t width, const uint8_t* coefs, const uint8_t* exps, const uint32_t* counts,
+                    uint64_t total);
+
 // ---- api_stark.hip --------------------------------------------------------------------------------------
 // Device layout of the step-polynomial description (one allocation, ctx->terms_dev)
 struct TermLayout {

@@ -1,5 +1,7 @@
 // modverify.hip -- the host verifier of FRI proofs over any odd modulus below 2^256 (host code only; no kernel, no context, no GPU):
 //   shk::mod_fri_verify = SmoothSubgroupFRI.verify_proximity_proof (starks/fri.py:268-366) over IntegersModP(p)
+//   shk::mod_stark_verify = STARK.verify_proof (starks/stark.py:281-388) over IntegersModP(p), on sh_mod_stark_prove's flat proofs, at the
+//                           end of this file: the FRI proof of the linear combination by the code below, then the spot checks
 // on the FLAT proofs sh_mod_fri_prove writes (the layout of sh_fri_prove, include/starkhip.h).  It walks one proof serially, as verify.hip
 // walks a MiMC proof, on the run-time-modulus arithmetic of fpm.cuh, and shares no code with the batch path (modverify_items.cuh): it
 // is the yardstick the batch verifier's statuses are compared with.
@@ -83,6 +85,31 @@ bool m_verify_branch(const uint8_t root[32], uint64_t index, const uint8_t* proo
       m_blake_pair(proof + 32 * e, v, d);
     else
       m_blake_pair(v, proof + 32 * e, d);
+    memcpy(v, d, 32);
+  }
+  return memcmp(v, root, 32) == 0;
+}
+
+// the same on a branch of a packed tree (merkle_tree.py:94-119): leaf (leaf_bytes) | sibling leaf (leaf_bytes) | entries - 2 nodes
+bool m_verify_packed_branch(const uint8_t root[32], uint64_t index, const uint8_t* proof, uint32_t entries, size_t leaf_bytes) {
+  if (entries < 2) return false;
+  const uint64_t half = 1ull << (entries - 1);
+  const uint64_t q = half / 4;
+  if (q == 0 || index >= half) return false;
+  uint64_t idx = index / q + 4 * (index % q) + half;
+  std::vector<uint8_t> buf(2 * leaf_bytes);
+  memcpy(buf.data(), idx & 1 ? proof + leaf_bytes : proof, leaf_bytes);
+  memcpy(buf.data() + leaf_bytes, idx & 1 ? proof : proof + leaf_bytes, leaf_bytes);
+  uint8_t v[32];
+  m_blake(buf.data(), buf.size(), v);
+  idx >>= 1;
+  const uint8_t* node = proof + 2 * leaf_bytes;
+  for (uint32_t e = 2; e < entries; ++e, node += 32, idx >>= 1) {
+    uint8_t d[32];
+    if (idx & 1)
+      m_blake_pair(node, v, d);
+    else
+      m_blake_pair(v, node, d);
     memcpy(v, d, 32);
   }
   return memcmp(v, root, 32) == 0;
@@ -298,5 +325,110 @@ int mod_fri_verify(const uint8_t modulus[32], const uint8_t* proof, uint64_t pro
   const fpm w = fpm_to_mont(wp, R.M);
   if (!fpm_eq(R.pow(w, n / 2), fpm_neg(R.one(), R.M))) return SH_ERR_ROOT_ORDER;
   return fri_verify(R, Cursor{proof, proof_len}, merkle_root, n, w, maxdeg_plus_1, exclude_multiples_of, samples);
+}
+
+// STARK.verify_proof + verify_proof_at_position (stark.py:281-388) over IntegersModP(p) on the flat proof of sh_mod_stark_prove
+// (the layout of sh_stark_prove): the FRI proof of the linear combination against l_root, then per sampled position the three Merkle
+// branches, the transition constraint and the boundary constraint.  (The linear-combination check is commented out in the reference,
+// stark.py:376-384, and is not made.)  Every value -- proof, inputs, outputs, coefficients -- is any 256-bit number taken modulo p.
+// The two denominators x - x_last and x_last - 1 are inverted by mod_inverse; both are units wherever G2^(n/2) = -1 (G2 has order n
+// modulo every prime factor of p; a sampled position is no multiple of ext, and 0 < (steps - 1) ext < n).
+int mod_stark_verify(const uint8_t modulus[32], const uint8_t* proof, uint64_t proof_len, const uint8_t* inputs, const uint8_t* outputs,
+                     uint64_t steps, uint32_t ext, uint32_t width, const uint8_t* term_coefs, const uint8_t* term_exps,
+                     const uint32_t* term_counts, uint32_t samples) {
+  if (!modulus || !proof || !inputs || !outputs || !term_coefs || !term_exps || !term_counts) return SH_ERR_INVALID;
+  Ring R;
+  if (!fpm_mod_init(modulus, &R.M)) return SH_ERR_INVALID;  // even, 0 or 1
+  if (width == 0 || samples == 0) return SH_ERR_INVALID;
+  if (steps < 2 || (steps & (steps - 1)) || ext < 2 || (ext & (ext - 1))) return SH_ERR_INVALID;
+  if (steps >= (1ull << 24) || ext >= (1u << 24) || steps * ext >= (1ull << 24)) return SH_ERR_INVALID;  // utils.py:69 (no wrap-around)
+  if (width > 9) return SH_ERR_UNSUPPORTED;  // get_pseudorandom_ks returns None from 10 on (stark.py:106-126)
+  const uint64_t n = steps * ext;
+  const uint32_t lg = (uint32_t)ilog2u(n), k = 3 * width;
+  uint32_t degree = 0;
+  uint64_t total = 0;
+  std::vector<uint32_t> tbegin(width + 1, 0);
+  for (uint32_t d = 0; d < width; ++d) {
+    if (term_counts[d] > 256) return SH_ERR_UNSUPPORTED;
+    tbegin[d] = (uint32_t)total;
+    total += term_counts[d];
+  }
+  tbegin[width] = (uint32_t)total;
+  if (total > 256) return SH_ERR_UNSUPPORTED;
+  if (total == 0) return SH_ERR_INVALID;
+  std::vector<fpm> coef(total);
+  for (uint32_t t = 0; t < total; ++t) {
+    coef[t] = R.to_m(term_coefs + 32 * t);
+    uint32_t sum = 0;
+    for (uint32_t v = 0; v < width; ++v) sum += term_exps[(size_t)t * width + v];
+    if (sum > degree) degree = sum;  // as sh_mod_stark_prove takes it: every listed term counts
+  }
+  // G2 = 7^((p - 1) // n) (stark.py:205): p - 1 is p without its low bit, the division a shift
+  fpm g2 = R.one();
+  {
+    fpm b = fpm_to_mont(fpm_from_u32(7u), R.M);
+    for (uint32_t i = lg; i < 256; ++i) {  // bit i of p - 1 is bit i - lg of the exponent
+      const uint32_t bit = i == 0 ? 0u : (R.M.p[i / 32] >> (i % 32)) & 1u;
+      if (bit) g2 = R.mul(g2, b);
+      b = R.mul(b, b);
+    }
+  }
+  if (!fpm_eq(R.pow(g2, n / 2), fpm_neg(R.one(), R.M))) return SH_ERR_ROOT_ORDER;
+  Cursor cur{proof, proof_len};
+  const uint8_t* m_root = cur.take(32);
+  const uint8_t* l_root = cur.take(32);
+  if (!m_root || !l_root) return SH_ERR_INVALID;
+  const uint64_t pb = 32ull * (2 * k + (lg - 1)), lb = 32ull * (lg + 1);
+  if (cur.left / (2 * pb + lb) < samples) return SH_ERR_INVALID;  // before anything is derived from `samples`: a hostile count costs nothing
+  const uint8_t* branches = cur.take((2 * pb + lb) * samples);
+  if (!branches) return SH_ERR_INVALID;
+  // the low-degree proof of the linear combination (stark.py:287-289)
+  const int rc = fri_verify(R, cur, l_root, n, g2, steps * (uint64_t)degree, ext, 40);
+  if (rc != SH_OK) return rc;
+  std::vector<uint32_t> pos;
+  if (!m_sample_indices(l_root, n, samples, ext, &pos)) return SH_ERR_INVALID;
+  const fpm r2 = fpm_from_words(R.M.r2);
+  const fpm last = R.pow(g2, (steps - 1) * ext);
+  fpm inv;
+  if (!mod_inverse(R, fpm_from_mont(R.sub(last, R.one()), R.M), &inv)) return SH_ERR_ROOT_ORDER;  // (unreachable: a unit, see above)
+  const fpm inv_last_m1 = R.mul(inv, r2);
+  std::vector<fpm> px(width), dx(width), bx(width), pg(width);
+  for (uint32_t i = 0; i < samples; ++i) {
+    const uint8_t* b1 = branches + (2 * pb + lb) * i;
+    const uint8_t* b2 = b1 + pb;
+    const uint8_t* b3 = b2 + pb;
+    const uint64_t x_i = pos[i];
+    if (!m_verify_packed_branch(m_root, x_i, b1, lg + 1, 32 * k)) return SH_ERR_REJECTED;
+    if (!m_verify_packed_branch(m_root, (x_i + ext) % n, b2, lg + 1, 32 * k)) return SH_ERR_REJECTED;
+    if (!m_verify_branch(l_root, x_i, b3, lg + 1)) return SH_ERR_REJECTED;
+    for (uint32_t d = 0; d < width; ++d) {
+      px[d] = R.to_m(b1 + 32 * d);
+      dx[d] = R.to_m(b1 + 32 * (width + d));
+      bx[d] = R.to_m(b1 + 32 * (2 * width + d));
+      pg[d] = R.to_m(b2 + 32 * d);
+    }
+    const fpm x = R.pow(g2, x_i);
+    const fpm xm = R.sub(x, last);
+    if (!mod_inverse(R, fpm_from_mont(xm, R.M), &inv)) return SH_ERR_REJECTED;  // the sampling excludes the trace points
+    const fpm zvalue = R.mul(R.sub(R.pow(x, steps), R.one()), R.mul(inv, r2));  // Z(x) = (x^steps - 1) / (x - x_last)
+    const fpm z2 = R.mul(R.sub(x, R.one()), xm);
+    for (uint32_t d = 0; d < width; ++d) {
+      // transition constraint: P_d(g1 x) - step_d(P(x)) = Z(x) D_d(x) (stark.py:355-365)
+      fpm acc = fpm_zero();
+      for (uint32_t t = tbegin[d]; t < tbegin[d + 1]; ++t) {
+        fpm prod = coef[t];
+        for (uint32_t v = 0; v < width; ++v)
+          for (uint32_t e = 0; e < term_exps[(size_t)t * width + v]; ++e) prod = R.mul(prod, px[v]);
+        acc = R.add(acc, prod);
+      }
+      if (!fpm_eq(R.sub(pg[d], acc), R.mul(zvalue, dx[d]))) return SH_ERR_REJECTED;
+      // boundary constraint: B_d(x) Z2(x) + I_d(x) = P_d(x), I_d through (1, input), (x_last, output) (stark.py:367-374)
+      const fpm in = R.to_m(inputs + 32 * d), out = R.to_m(outputs + 32 * d);
+      const fpm slope = R.mul(R.sub(out, in), inv_last_m1);
+      const fpm interp = R.add(R.sub(in, slope), R.mul(slope, x));
+      if (!fpm_eq(R.sub(px[d], R.mul(bx[d], z2)), interp)) return SH_ERR_REJECTED;
+    }
+  }
+  return SH_OK;
 }
 }  // namespace shk

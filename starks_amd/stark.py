@@ -180,6 +180,32 @@ def verify_flat_batch(flats, input_bytes, output_bytes, steps, ext, width, step_
     return [s == 0 for s in status]
 
 
+def mod_verify_flat(modulus, flat, input_bytes, output_bytes, steps, ext, width, step_polys, samples=SPOT_CHECKS):
+    """verify_flat over any prime modulus below 2^256 (sh_mod_stark_verify: host C++, no context, no GPU; the decisions of
+    STARK.verify_proof over IntegersModP(modulus)) on a FLAT proof as mod_prove_flat returns it.  Every value is taken modulo `modulus`."""
+    coefs, exps, counts, _ = pack_step_polys(step_polys, width, p=modulus)
+    rc = _lib.lib().sh_mod_stark_verify(int(modulus).to_bytes(32, "big"), bytes(flat), len(flat), bytes(input_bytes), bytes(output_bytes),
+                                        steps, ext, width, coefs, exps, counts, samples)
+    if rc == -9:
+        raise AssertionError("STARK proof rejected")
+    _lib.check(rc, "sh_mod_stark_verify")
+    return True
+
+
+def mod_verify_flat_batch(modulus, flats, input_bytes, output_bytes, steps, ext, width, step_polys, batch, samples=SPOT_CHECKS):
+    """verify_flat_batch over any prime modulus below 2^256 (sh_mod_stark_verify_batch): `batch` flat proofs of one shape verified on the
+    GPU in one call.  -> [bool] per proof, each the decision mod_verify_flat takes on that proof alone."""
+    coefs, exps, counts, _ = pack_step_polys(step_polys, width, p=modulus)
+    flats = bytes(flats)
+    if batch < 1 or len(flats) % batch:
+        raise ValueError("flats must hold batch proofs of equal length")
+    status = (ctypes.c_int32 * batch)()
+    rc = _lib.lib().sh_mod_stark_verify_batch(_lib.ctx(), int(modulus).to_bytes(32, "big"), flats, len(flats) // batch, bytes(input_bytes),
+                                              bytes(output_bytes), steps, ext, width, coefs, exps, counts, samples, batch, status)
+    _lib.check(rc, "sh_mod_stark_verify_batch")  # a shape error, or a proof length that is not the shape's
+    return [s == 0 for s in status]
+
+
 def witness_flat(input_bytes, steps, width, step_polys, batch=1):
     """AIR.generate_witness / get_computational_trace (air.py:32-52, 121-123) on the GPU (sh_stark_witness): input_bytes [batch][width]
     wire form (values may be >= p) -> the witness [batch][width][steps] in wire form, what prove_flat takes.  Any steps >= 1."""
@@ -297,6 +323,15 @@ class STARK(object):
         outputs = _lib.to_wire([col[-1] for col in witness])
         return verify_flat(pack_proof(proof), inputs, outputs, self.steps, self.extension_factor, self.width, self.step_polys,
                            self.spot_check_security_factor)
+
+    def verify_proof_mod_native(self, proof, witness, boundary):
+        """The same decision from the library's C verifier over a run-time modulus (sh_mod_stark_verify) on the packed proof, for
+        whatever modulus the STARK was built over, the MiMC prime included."""
+        p = self.modulus
+        inputs = _lib.to_wire([constraint[2] for constraint in boundary[:self.width]], p)
+        outputs = _lib.to_wire([col[-1] for col in witness], p)
+        return mod_verify_flat(p, pack_proof(proof), inputs, outputs, self.steps, self.extension_factor, self.width, self.step_polys,
+                               self.spot_check_security_factor)
 
     def verify_proof_at_position(self, witness, boundary, ks, proof, i, pos):
         """stark.py:318-388 (the linear-combination check is commented out there, :376-384, and is not made here)."""
