@@ -16,6 +16,28 @@ def get_computational_trace(inp, steps, width, step_polys):
     return trace, trace[-1]
 
 
+def device_witness(field, inp, steps, step_polys):
+    """AIR(...).generate_witness() on the GPU: witness[dim] as one WireList of `steps` elements of `field` per dimension.  The MiMC
+    field goes through sh_stark_witness, any other odd modulus below 2^256 through sh_mod_stark_witness (stark.witness_flat /
+    stark.mod_witness_flat); inputs may be ints or field elements.  `AIR` itself stays host-side Python."""
+    from . import stark
+    from ._lib import MIMC_P
+    from .wireseq import WireList
+    if isinstance(inp, int):  # air.py:89-90
+        inp = [inp]
+    p, width = int(field.p), len(step_polys)
+    if len(inp) != width:
+        raise ValueError("%d inputs for %d step polynomials" % (len(inp), width))
+    raw = b"".join((int(v) % p).to_bytes(32, "big") for v in inp)
+    if p == MIMC_P:
+        flat = stark.witness_flat(raw, steps, width, step_polys)
+    else:
+        if p < 3 or p % 2 == 0 or p >> 256:
+            raise NotImplementedError("device_witness takes odd moduli 3 <= p < 2^256 (got %d)" % p)
+        flat = stark.mod_witness_flat(p, raw, steps, width, step_polys)
+    return [WireList(flat[32 * steps * d:32 * steps * (d + 1)], field) for d in range(width)]
+
+
 class AIR(object):
     def __init__(self, field, width, inp, steps, step_polys, extension_factor):
         self.field = field

@@ -1,6 +1,7 @@
 // api_modstark.hip -- STARK.mk_proof (stark.py:233-279) over any prime modulus below 2^256 on the host side, and its entry points: the
 // transforms are api_modntt.hip's, the middle of the prover modstark.hip's, the commit rounds api_modfri.hip's (modfri_rounds, on the
 // evaluations and the tree built here), the tree levels above the leaf kernels and the index sampler the MiMC path's (kernels.hip).
+// Also AIR.generate_witness over any odd modulus (sh_mod_stark_witness, sh_dev_mod_stark_witness: modwitness.hip launched in slices).
 // Every check runs on the host before anything is launched.
 #include "ctx.hpp"
 #include "modstark_items.cuh"
@@ -231,6 +232,53 @@ int run_mod_stark(sh_ctx* c, const ModStarkCall& sc, fpm* d_wit, const fpm* d_in
   return modfri_rounds(c, sc.fwd_n, tw_n, fb, n, steps * (uint64_t)sc.degree, ext, 40, batch,
                        d_proof + stark_header_len(n, width, samples), sc.stride, true);
 }
+
+// ---- AIR.generate_witness (air.py:32-52, 121-123) over any odd modulus: modwitness.hip, launched in slices of steps ---------------------
+// every host check of a witness call but the null pointers; on SH_OK M holds the modulus block and *total the number of terms
+int mod_witness_check(sh_ctx* c, const char* who, const uint8_t modulus[32], uint64_t steps, uint32_t width, const uint32_t* counts,
+                      uint32_t batch, fpm_mod* M, uint64_t* total) {
+  if (!fpm_mod_init(modulus, M)) return refuse(c, who, SH_ERR_INVALID, "the modulus must be odd and at least 3");
+  if (steps == 0 || width == 0 || batch == 0) return refuse(c, who, SH_ERR_INVALID, "steps, width and batch must be at least 1");
+  if (width > SHK_STARK_MAX_WIDTH) return refuse(c, who, SH_ERR_UNSUPPORTED, "width is limited to 9 (stark.py:106-126)");
+  *total = 0;
+  for (uint32_t d = 0; d < width; ++d) *total += counts[d];
+  if (*total == 0) return refuse(c, who, SH_ERR_INVALID, "the step polynomials have no terms");
+  if (*total > SHK_STARK_MAX_TERMS) return refuse(c, who, SH_ERR_UNSUPPORTED, "more step-polynomial terms than SHK_STARK_MAX_TERMS");
+  const uint64_t cols = (uint64_t)batch * width;
+  if (cols > 0xffffffffull || steps > (~0ull / 32) / cols)
+    return refuse(c, who, SH_ERR_UNSUPPORTED, "batch * width must be below 2^32 and the witness's byte count must fit 64 bits");
+  return SH_OK;
+}
+
+// d_wit [batch][width][steps], plain and canonical, from d_in [batch][width]; the terms are the ones mod_stark_terms just uploaded.
+// The plan comes from the caller's term bytes: a coefficient counts as 1 when it is 1 modulo p, as the kernel derives it from the image.
+int run_mod_witness(sh_ctx* c, const fpm_mod& M, const fpm* d_in, fpm* d_wit, uint64_t steps, uint32_t width, const uint8_t* coefs,
+                    const uint8_t* exps, const uint32_t* counts, uint32_t batch) {
+  WiRow rows[SHK_STARK_MAX_TERMS];
+  uint32_t T = 0;
+  for (uint32_t d = 0; d < width; ++d)
+    for (uint32_t i = 0; i < counts[d]; ++i, ++T)
+      rows[T] = wi_pack_row(d, mwi_unit(fpm_to_mont(fpm_from_wire_bytes(coefs + 32ull * T), M), M), exps + (size_t)T * width, width);
+  ModWitnessArgs a;
+  memset(&a, 0, sizeof a);
+  mwi_plan(rows, T, width, (uint32_t)shk_knobs().witness_group, (uint64_t)shk_knobs().witness_slice, &a.plan);
+  const bool inl = shk_knobs().witness_inline;
+  const uint8_t* tb = reinterpret_cast<const uint8_t*>(c->mod_terms_dev);
+  a.inputs = d_in;
+  a.wit = d_wit;
+  a.steps = steps;
+  a.batch = batch;
+  a.nterms = T;
+  a.coef = reinterpret_cast<const fpm*>(tb + ModTermLayout::coef);
+  a.exps = tb + ModTermLayout::exps;
+  memcpy(a.begin, c->mod_terms_begin, sizeof a.begin);
+  for (a.k0 = 0; a.k0 < steps; a.k0 = a.k1) {  // each dispatch resumes from the last row the previous one wrote
+    a.k1 = steps - a.k0 > a.plan.slice ? a.k0 + a.plan.slice : steps;
+    HIP_TRY(c, shk_mod_witness_slice(a, M, width, inl, c->stream));
+  }
+  if (!inl) HIP_TRY(c, shk_mod_witness_finish(d_wit, (uint64_t)batch * width * steps, M, c->stream));
+  return SH_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -279,5 +327,51 @@ int sh_mod_stark_prove(sh_ctx* c, const uint8_t modulus[32], const uint8_t* witn
   SH_TRY(run_mod_stark(c, sc, dwit, dwit + wn, steps, ext, width, samples, batch, reinterpret_cast<uint8_t*>(dp)));
   SH_TRY(d2h(c, proof, dp, (size_t)sc.stride * batch));
   return sh_stark_status(c);
+}
+
+int sh_dev_mod_stark_witness(sh_ctx* c, const uint8_t modulus[32], const void* d_inputs, uint64_t steps, uint32_t width,
+                             const uint8_t* term_coefs, const uint8_t* term_exps, const uint32_t* term_counts, uint32_t batch,
+                             void* d_witness) {
+  const char* who = "sh_dev_mod_stark_witness";
+  if (!c) return SH_ERR_INVALID;
+  if (!modulus || !d_inputs || !term_coefs || !term_exps || !term_counts || !d_witness) return refuse(c, who, SH_ERR_INVALID, "null pointer");
+  fpm_mod M;
+  uint64_t total = 0;
+  SH_TRY(mod_witness_check(c, who, modulus, steps, width, term_counts, batch, &M, &total));
+  if (any_overlap(d_inputs, 32ull * batch * width, d_witness, 32ull * batch * width * steps))
+    return refuse(c, who, SH_ERR_INVALID, "d_inputs and d_witness overlap");
+  SH_TRY(enter(c));
+  SH_TRY(mod_stark_terms(c, M, width, term_coefs, term_exps, term_counts, total));
+  return run_mod_witness(c, M, reinterpret_cast<const fpm*>(d_inputs), reinterpret_cast<fpm*>(d_witness), steps, width, term_coefs,
+                         term_exps, term_counts, batch);
+}
+
+int sh_mod_stark_witness(sh_ctx* c, const uint8_t modulus[32], const uint8_t* inputs, uint64_t steps, uint32_t width,
+                         const uint8_t* term_coefs, const uint8_t* term_exps, const uint32_t* term_counts, uint32_t batch, uint8_t* witness,
+                         uint64_t witness_cap) {
+  const char* who = "sh_mod_stark_witness";
+  if (!c) return SH_ERR_INVALID;
+  if (!modulus || !inputs || !term_coefs || !term_exps || !term_counts || !witness) return refuse(c, who, SH_ERR_INVALID, "null pointer");
+  fpm_mod M;
+  uint64_t total = 0;
+  SH_TRY(mod_witness_check(c, who, modulus, steps, width, term_counts, batch, &M, &total));
+  const uint64_t cols = (uint64_t)batch * width, count = cols * steps;
+  if (witness_cap / 32 < count) return refuse(c, who, SH_ERR_TOO_SMALL, "witness_cap is below 32 * batch * width * steps");
+  SH_TRY(enter(c));
+  SH_TRY(mod_stark_terms(c, M, width, term_coefs, term_exps, term_counts, total));
+  // wire form <-> limbs is a byte reversal per value; nothing is reduced on the host (row 0 reduces an input >= p on the device)
+  std::vector<uint8_t> limbs((size_t)cols * 32);
+  for (uint64_t i = 0; i < cols; ++i)
+    for (int k = 0; k < 32; ++k) limbs[32 * i + k] = inputs[32 * i + 31 - k];
+  void *in = nullptr, *w = nullptr;
+  SH_TRY(ws_get(c, sh_ctx::WS_Y, limbs.size(), &in));
+  SH_TRY(ws_get(c, sh_ctx::WS_ST_TRACE, (size_t)count * sizeof(fpm), &w));
+  SH_TRY(h2d(c, in, limbs.data(), limbs.size()));
+  SH_TRY(run_mod_witness(c, M, reinterpret_cast<const fpm*>(in), reinterpret_cast<fpm*>(w), steps, width, term_coefs, term_exps,
+                         term_counts, batch));
+  SH_TRY(d2h(c, witness, w, (size_t)count * 32));
+  for (uint64_t i = 0; i < count; ++i)
+    for (int k = 0; k < 16; ++k) std::swap(witness[32 * i + k], witness[32 * i + 31 - k]);
+  return SH_OK;
 }
 }  // extern "C"

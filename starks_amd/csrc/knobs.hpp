@@ -18,6 +18,9 @@
 //                                  (ntt_narrow_pass_kernel; default 256 = the CUs of the chip; 0 = never)
 //   STARKHIP_WITNESS_GROUP=1|2|4|8|16  lanes per unit of the witness generator (witness.hip; default: chosen from the term table)
 //   STARKHIP_WITNESS_SLICE=k       steps per witness dispatch (default: about 2^13 sequential products per dispatch, at least 1)
+//                                  (over another modulus, modwitness.hip: about 2^12, modwitness_items.cuh).  Both apply to both paths
+//   STARKHIP_WITNESS_STORE=pass|inline  how the generic witness generator reaches plain form: one closing pass over the witness
+//                                  (default), or a conversion on the kernel's store path (modwitness_items.cuh; tools/mod_witness_time.py)
 //   STARKHIP_EVAL_PATH=direct|tree  the path of every sh_poly_eval call (default: chosen per call, poly_items.cuh:pe_direct_preferred)
 //   STARKHIP_MODNTT_TILE_LOG=2..10 elements per tile (log2) of the generic transform (modntt_items.cuh; default 10): small values force
 //                                  plans of many passes at small n (tests/test_gpu_modntt.py)
@@ -46,6 +49,7 @@ struct ShkKnobs {
   long narrow_tiles = 256;   // 0: the narrow form is never used
   int witness_group = 0;     // 0: not given
   long witness_slice = 0;    // 0: not given
+  bool witness_inline = false;  // generic witness generator: convert on the store path instead of in a closing pass
   int eval_path = 0;         // 0: chosen per call, 1: direct, 2: tree
   int modntt_tile_log = 10;  // generic transform: 2 .. 10
   int mod64_tile_log = 12;   // packed-word transform: 2 .. 13
@@ -97,6 +101,7 @@ inline void parse(ShkKnobs* k) {
     const long v = atol(e);
     if (v > 0) k->witness_slice = v;
   }
+  if (const char* e = getenv("STARKHIP_WITNESS_STORE")) k->witness_inline = std::string(e) == "inline";
   if (const char* e = getenv("STARKHIP_EVAL_PATH")) {
     const std::string v(e);
     k->eval_path = v == "direct" ? 1 : v == "tree" ? 2 : 0;

@@ -258,6 +258,63 @@ def prove_inputs_flat(input_bytes, steps, ext, width, step_polys, batch=1, sampl
     return proofs.raw, outputs
 
 
+def mod_witness_flat(modulus, input_bytes, steps, width, step_polys, batch=1):
+    """witness_flat over any odd modulus 3 <= p < 2^256, composite ones included (sh_mod_stark_witness): input_bytes [batch][width]
+    wire form (values may be >= p) -> the witness [batch][width][steps] in canonical wire form, what mod_prove_flat takes.  Any
+    steps >= 1."""
+    if len(input_bytes) != 32 * batch * width:
+        raise ValueError("inputs must hold batch*width 32-byte elements (got %d bytes for batch=%d, width=%d)"
+                         % (len(input_bytes), batch, width))
+    coefs, exps, counts, _ = pack_step_polys(step_polys, width, p=modulus)
+    nbytes = 32 * batch * width * steps
+    out = ctypes.create_string_buffer(nbytes)
+    _lib.check(_lib.lib().sh_mod_stark_witness(_lib.ctx(), int(modulus).to_bytes(32, "big"), bytes(input_bytes), steps, width, coefs, exps,
+                                               counts, batch, out, nbytes), "sh_mod_stark_witness")
+    return out.raw
+
+
+def mod_prove_inputs_flat(modulus, input_bytes, steps, ext, width, step_polys, batch=1, samples=SPOT_CHECKS):
+    """prove_inputs_flat over any prime modulus the generic prover takes: upload the inputs as little-endian limbs, then
+    sh_dev_mod_stark_witness -> sh_dev_mod_stark_prove -> sh_stark_status on device buffers (the witness never leaves the device).
+    -> (batch flat proofs concatenated, outputs): outputs = witness[b][dim][-1] as [batch][width] wire form."""
+    if len(input_bytes) != 32 * batch * width:
+        raise ValueError("inputs must hold batch*width 32-byte elements (got %d bytes for batch=%d, width=%d)"
+                         % (len(input_bytes), batch, width))
+    coefs, exps, counts, degree = pack_step_polys(step_polys, width, p=modulus)
+    plen = proof_len(steps, ext, width, degree, samples)
+    if plen == 0:
+        raise NotImplementedError("starks_amd.STARK: unsupported shape (steps=%d, ext=%d, width=%d, degree=%d)"
+                                  % (steps, ext, width, degree))
+    L, ctx = _lib.lib(), _lib.ctx()
+    pb = int(modulus).to_bytes(32, "big")
+    raw_in = bytes(input_bytes)
+    limbs = b"".join(raw_in[i:i + 32][::-1] for i in range(0, len(raw_in), 32))  # wire form reversed = little-endian limbs
+    di, dw, dp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    try:
+        for ptr, nbytes in ((di, 32 * batch * width), (dw, 32 * batch * width * steps), (dp, plen * batch)):
+            _lib.check(L.sh_dev_alloc(ctx, nbytes, ctypes.byref(ptr)), "sh_dev_alloc")
+        _lib.check(L.sh_dev_upload(ctx, limbs, di, len(limbs)), "sh_dev_upload")
+        _lib.check(L.sh_dev_mod_stark_witness(ctx, pb, di, steps, width, coefs, exps, counts, batch, dw), "sh_dev_mod_stark_witness")
+        _lib.check(L.sh_dev_mod_stark_prove(ctx, pb, dw, di, steps, ext, width, coefs, exps, counts, samples, batch, dp),
+                   "sh_dev_mod_stark_prove")
+        rc = L.sh_stark_status(ctx)
+        if rc == -8:  # a generated witness is a valid trace by construction: this would be a library fault
+            raise AssertionError("constraint polynomial is not a multiple of Z: the generated witness is not a valid trace")
+        _lib.check(rc, "sh_stark_status")
+        proofs = ctypes.create_string_buffer(plen * batch)
+        _lib.check(L.sh_dev_download(ctx, dp, proofs, plen * batch), "sh_dev_download")
+        last = ctypes.create_string_buffer(32 * batch * width)  # witness[b][dim][steps - 1], plain canonical limbs
+        _lib.check(L.sh_dev_download_2d(ctx, ctypes.c_void_p(dw.value + 32 * (steps - 1)), 32 * steps, last, 32, batch * width),
+                   "sh_dev_download_2d")
+    finally:
+        for ptr in (di, dw, dp):
+            if ptr.value:
+                L.sh_dev_free(ctx, ptr)
+    raw = last.raw
+    outputs = b"".join(raw[i:i + 32][::-1] for i in range(0, len(raw), 32))
+    return proofs.raw, outputs
+
+
 class STARK(object):
     """Generates and verifies STARKs (stark.py:179-402); same constructor arguments."""
 

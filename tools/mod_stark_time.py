@@ -3,8 +3,8 @@
 width-2 cubic system (X1' = X1, X2' = X2^3 + X1; ext 8, 80 spot checks) over BN254 at 2^12, 2^16 and 2^20 steps and 64 x 2^12 steps,
 and over Goldilocks and the MiMC prime at 2^16 steps; in the same run sh_dev_stark_prove (the tuned MiMC prover) on the same shapes,
 and the transforms of a proof alone on both paths (the steps-point inverse, the short-input forward transform onto steps * ext points,
-the steps-point forward transform of X P'(X)).  Witnesses are valid traces over their own modulus (sh_dev_stark_witness for the MiMC
-prime, a Python trace uploaded once for the others).  HIP events around REPS calls after a warm-up of every shape (tables, workspaces,
+the steps-point forward transform of X P'(X)).  Witnesses are valid traces over their own modulus, generated on the device from the
+inputs (sh_dev_stark_witness for the tuned path, sh_dev_mod_stark_witness for the generic one).  HIP events around REPS calls after a warm-up of every shape (tables, workspaces,
 code objects), the smallest of ROUNDS windows, the paths alternating round by round.
 `proof_ratio_to_tuned` = generic proof / tuned proof; `middle_ratio` = (generic proof - generic transforms) / (tuned proof - tuned
 transforms): what the quotients, the trees, the combination, the gather and the commit rounds cost over p beside the tuned ones.
@@ -60,20 +60,6 @@ def window(L, ctx, fn, reps):
     return ms.value / reps
 
 
-def trace_limbs(p, steps, batch):
-    """[batch][2][steps] limb form of the system's trace from inputs (2 + b, 5 + b)"""
-    out = bytearray()
-    for b in range(batch):
-        a, x = 2 + b, 5 + b
-        col = []
-        for _ in range(steps):
-            col.append(x)
-            x = (x * x * x + a) % p
-        out += b"".join(int(a).to_bytes(32, "little") for _ in range(steps))
-        out += b"".join(int(v).to_bytes(32, "little") for v in col)
-    return bytes(out)
-
-
 def setup(L, ctx, name, lg, batch):
     """-> ({path name: call}, the device buffers to free) for one shape"""
     coefs = b"".join(b32(c) for _, c in TERMS)
@@ -91,8 +77,7 @@ def setup(L, ctx, name, lg, batch):
     inputs = b"".join(int(v).to_bytes(32, "little") for b in range(batch) for v in (2 + b, 5 + b))
     ck(L.sh_dev_upload(ctx, inputs, ig, len(inputs)), "upload")
     ck(L.sh_dev_upload(ctx, inputs, im, len(inputs)), "upload")
-    raw = trace_limbs(p, steps, batch)
-    ck(L.sh_dev_upload(ctx, raw, wg, len(raw)), "upload")
+    ck(L.sh_dev_mod_stark_witness(ctx, b32(p), ig, steps, WIDTH, coefs, exps, counts, batch, wg), "sh_dev_mod_stark_witness")
     ck(L.sh_dev_stark_witness(ctx, im, steps, WIDTH, coefs, exps, counts, batch, wm), "sh_dev_stark_witness")
     g2p = pow(7, (p - 1) // n, p)
     g2m = pow(7, (MIMC_P - 1) // n, MIMC_P)
