@@ -130,6 +130,10 @@ def lib():
         "sh_dev_mod_fri_prove": (i32, [c_p, u8p, c_p, u64, u64, u8p, u64, u32, u32, u32, c_p]),
         "sh_mod_fri_fold": (i32, [c_p, u8p, u8p, u64, u8p, u8p, c_p]),
         "sh_dev_merkelize_plain": (i32, [c_p, c_p, u64, u32, c_p]),
+        "sh_mod64_fri_prove": (i32, [c_p, u64, c_p, u64, u64, u64, u64, u32, u32, u32, c_p, u64]),
+        "sh_dev_mod64_fri_prove": (i32, [c_p, u64, c_p, u64, u64, u64, u64, u32, u32, u32, c_p]),
+        "sh_mod64_fri_fold": (i32, [c_p, u64, c_p, u64, u64, u8p, c_p]),
+        "sh_dev_mod64_merkelize": (i32, [c_p, c_p, u64, u32, c_p]),
         "sh_mod_fri_verify": (i32, [u8p, u8p, u64, u8p, u64, u8p, u64, u32, u32]),
         "sh_dev_mod_fri_verify": (i32, [c_p, u8p, c_p, c_p, u64, u8p, u64, u32, u32, u32, c_p]),
         "sh_mod_fri_verify_batch": (i32, [c_p, u8p, u8p, u64, u8p, u64, u8p, u64, u32, u32, u32, c_p]),

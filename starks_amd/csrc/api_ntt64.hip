@@ -4,32 +4,27 @@
 using namespace shk;
 
 namespace {
-// everything the host derives from (modulus, root, n, direction) before a launch; nothing here touches the device
-struct Mod64Call {
-  f64_mod M;
-  uint64_t root_mont;  // the effective root (inverted for an inverse transform), Montgomery form
-  uint64_t scale;      // plain form: 1, or n^-1 for an inverse
-  int log_n;
-};
+const char* const LIMIT = ": n and batch * n are limited to 2^28";  // after the entry point's name
+}
 
-const char* const LIMIT = "sh_mod64_ntt: n and batch * n are limited to 2^28";
-
-int m64_prepare(sh_ctx* c, uint64_t modulus, uint64_t root, uint64_t n, uint64_t batch, bool inverse, bool scaled, Mod64Call* mc) {
+namespace shk {
+int mod64_prepare(sh_ctx* c, uint64_t modulus, uint64_t root, uint64_t n, uint64_t batch, bool inverse, bool scaled, Mod64Call* mc,
+                  const char* who) {
   if (!is_pow2(n) || batch == 0) return SH_ERR_INVALID;
   if (n > (1ull << N64_MAX_LOG_N) || batch > (1ull << N64_MAX_LOG_N) || batch * n > (1ull << N64_MAX_LOG_N)) {
-    c->err = LIMIT;
+    c->err = std::string(who) + LIMIT;
     return SH_ERR_UNSUPPORTED;
   }
   if (!f64_mod_init(modulus, &mc->M)) {
-    c->err = "sh_mod64_ntt: the modulus must be odd and at least 3";
+    c->err = std::string(who) + ": the modulus must be odd and at least 3";
     return SH_ERR_INVALID;
   }
   if (root >= modulus) {
-    c->err = "sh_mod64_ntt: root is not below the modulus";
+    c->err = std::string(who) + ": root is not below the modulus";
     return SH_ERR_ROOT_ORDER;
   }
   if (!n64_check_root(root, n, mc->M)) {
-    c->err = "sh_mod64_ntt: root does not have order n in this ring";
+    c->err = std::string(who) + ": root does not have order n in this ring";
     return SH_ERR_ROOT_ORDER;
   }
   mc->log_n = ilog2(n);
@@ -41,7 +36,7 @@ int m64_prepare(sh_ctx* c, uint64_t modulus, uint64_t root, uint64_t n, uint64_t
 
 // the tables of (modulus, effective root, n) -- lo | hi | stw in one allocation: a plan like any other -- same map, same byte budget,
 // same LRU pass, same statistics
-int m64_table(sh_ctx* c, const Mod64Call& mc, const uint64_t** out) {
+int mod64_table(sh_ctx* c, const Mod64Call& mc, const uint64_t** out) {
   *out = nullptr;
   if (mc.log_n == 0) return SH_OK;
   std::string key("m64:");
@@ -73,7 +68,7 @@ int m64_table(sh_ctx* c, const Mod64Call& mc, const uint64_t** out) {
 }
 
 // src [batch][n_in] -> dst [batch][n]; src may be dst when n_in == n
-int m64_run(sh_ctx* c, const Mod64Call& mc, const uint64_t* tab, const void* src, uint64_t n_in, void* dst, uint32_t batch) {
+int mod64_run(sh_ctx* c, const Mod64Call& mc, const uint64_t* tab, const void* src, uint64_t n_in, void* dst, uint32_t batch) {
   int radix[N64_MAX_PASSES];
   const int tile_log = shk_knobs().mod64_tile_log, m = n64_plan(mc.log_n, tile_log, radix);
   N64Tw t = {};
@@ -93,7 +88,7 @@ int m64_run(sh_ctx* c, const Mod64Call& mc, const uint64_t* tab, const void* src
   }
   return SH_OK;
 }
-}  // namespace
+}  // namespace shk
 
 extern "C" {
 
@@ -101,7 +96,7 @@ int sh_dev_mod64_ntt(sh_ctx* c, uint64_t modulus, const void* d_in, uint64_t n_i
                      uint64_t root, int inverse) {
   if (!c || !d_in || !d_out) return SH_ERR_INVALID;
   Mod64Call mc;
-  SH_TRY(m64_prepare(c, modulus, root, n, batch, inverse != 0, inverse != 0, &mc));
+  SH_TRY(mod64_prepare(c, modulus, root, n, batch, inverse != 0, inverse != 0, &mc));
   if (n_in > n) return SH_ERR_INVALID;
   if (d_in == d_out ? n_in != n : any_overlap(d_in, (uint64_t)batch * n_in * 8, d_out, (uint64_t)batch * n * 8)) {
     c->err = "sh_dev_mod64_ntt: d_in and d_out overlap (d_in == d_out is allowed when n_in == n)";
@@ -109,28 +104,28 @@ int sh_dev_mod64_ntt(sh_ctx* c, uint64_t modulus, const void* d_in, uint64_t n_i
   }
   SH_TRY(enter(c));
   const uint64_t* tab = nullptr;
-  SH_TRY(m64_table(c, mc, &tab));
-  return m64_run(c, mc, tab, d_in, n_in, d_out, batch);
+  SH_TRY(mod64_table(c, mc, &tab));
+  return mod64_run(c, mc, tab, d_in, n_in, d_out, batch);
 }
 
 int sh_mod64_ntt(sh_ctx* c, uint64_t modulus, const uint64_t* in, uint64_t n_in, uint64_t* out, uint64_t n, uint32_t batch,
                  uint64_t root, int inverse) {
   if (!c || !out || (n_in && !in)) return SH_ERR_INVALID;
   if (n_in > (1ull << N64_MAX_LOG_N)) {
-    c->err = LIMIT;
+    c->err = std::string("sh_mod64_ntt") + LIMIT;
     return SH_ERR_UNSUPPORTED;
   }
   Mod64Call mc;
-  SH_TRY(m64_prepare(c, modulus, root, n, batch, inverse != 0, inverse != 0, &mc));
+  SH_TRY(mod64_prepare(c, modulus, root, n, batch, inverse != 0, inverse != 0, &mc));
   if (n_in > n) return SH_ERR_INVALID;
   SH_TRY(enter(c));
   const uint64_t* tab = nullptr;
-  SH_TRY(m64_table(c, mc, &tab));
+  SH_TRY(mod64_table(c, mc, &tab));
   void *w = nullptr, *x = nullptr;
   SH_TRY(ws_get(c, sh_ctx::WS_WIRE, (size_t)batch * n_in * 8, &w));
   SH_TRY(ws_get(c, sh_ctx::WS_X, (size_t)batch * n * 8, &x));
   SH_TRY(h2d(c, w, in, (size_t)batch * n_in * 8));
-  SH_TRY(m64_run(c, mc, tab, w, n_in, x, batch));  // the zeros beyond n_in are never stored
+  SH_TRY(mod64_run(c, mc, tab, w, n_in, x, batch));  // the zeros beyond n_in are never stored
   return d2h(c, out, x, (size_t)batch * n * 8);
 }
 
@@ -138,25 +133,25 @@ int sh_mod64_mul_polys(sh_ctx* c, uint64_t modulus, const uint64_t* a, uint64_t 
                        uint64_t n, uint64_t root) {
   if (!c || !out || (n_a && !a) || (n_b && !b)) return SH_ERR_INVALID;
   Mod64Call fwd, rev;
-  SH_TRY(m64_prepare(c, modulus, root, n, 1, false, false, &fwd));
-  SH_TRY(m64_prepare(c, modulus, root, n, 1, true, false, &rev));  // reversed roots, NO 1/n (fft.py:345)
+  SH_TRY(mod64_prepare(c, modulus, root, n, 1, false, false, &fwd));
+  SH_TRY(mod64_prepare(c, modulus, root, n, 1, true, false, &rev));  // reversed roots, NO 1/n (fft.py:345)
   if (n_a > n || n_b > n) return SH_ERR_INVALID;
   SH_TRY(enter(c));
   const uint64_t *tf = nullptr, *tr = nullptr;
-  SH_TRY(m64_table(c, fwd, &tf));
-  SH_TRY(m64_table(c, rev, &tr));
+  SH_TRY(mod64_table(c, fwd, &tf));
+  SH_TRY(mod64_table(c, rev, &tr));
   void *w = nullptr, *x = nullptr, *y = nullptr, *z = nullptr;
   SH_TRY(ws_get(c, sh_ctx::WS_WIRE, (size_t)(n_a > n_b ? n_a : n_b) * 8, &w));
   SH_TRY(ws_get(c, sh_ctx::WS_X, (size_t)n * 8, &x));
   SH_TRY(ws_get(c, sh_ctx::WS_Y, (size_t)n * 8, &y));
   SH_TRY(ws_get(c, sh_ctx::WS_MISC, (size_t)n * 8, &z));
   SH_TRY(h2d(c, w, a, (size_t)n_a * 8));
-  SH_TRY(m64_run(c, fwd, tf, w, n_a, x, 1));
+  SH_TRY(mod64_run(c, fwd, tf, w, n_a, x, 1));
   SH_TRY(h2d(c, w, b, (size_t)n_b * 8));
-  SH_TRY(m64_run(c, fwd, tf, w, n_b, y, 1));
+  SH_TRY(mod64_run(c, fwd, tf, w, n_b, y, 1));
   HIP_TRY(c, shk_n64_pointwise(reinterpret_cast<const uint64_t*>(x), reinterpret_cast<const uint64_t*>(y), reinterpret_cast<uint64_t*>(x),
                                n, fwd.M, c->stream));
-  SH_TRY(m64_run(c, rev, tr, x, n, z, 1));
+  SH_TRY(mod64_run(c, rev, tr, x, n, z, 1));
   return d2h(c, out, z, (size_t)n * 8);
 }
 

@@ -237,6 +237,34 @@ int mod_run(sh_ctx* c, const ModCall& mc, const fpm* tw, const void* src, uint64
 int modfri_rounds(sh_ctx* c, const ModCall& mc, const fpm* tw, FriBuffers fb, uint64_t n, uint64_t maxdeg_plus_1, uint32_t exclude,
                   uint32_t samples, uint32_t batch, uint8_t* d_proof, uint64_t stride, bool have_tree);
 
+// ---- api_ntt64.hip --------------------------------------------------------------------------------------
+// everything the host derives from (modulus, root, n, direction) before a packed-word launch; nothing here touches the device
+struct Mod64Call {
+  f64_mod M;
+  uint64_t root_mont;  // the effective root (inverted for an inverse transform), Montgomery form
+  uint64_t scale;      // plain form: 1, or n^-1 for an inverse
+  int log_n;
+};
+// every check of a packed-word call, on the host; `who` opens the sh_last_error text
+int mod64_prepare(sh_ctx* c, uint64_t modulus, uint64_t root, uint64_t n, uint64_t batch, bool inverse, bool scaled, Mod64Call* mc,
+                  const char* who = "sh_mod64_ntt");
+// the tables of (modulus, effective root, n) -- lo | hi | stw in one allocation, Montgomery form --, held in the plan cache
+int mod64_table(sh_ctx* c, const Mod64Call& mc, const uint64_t** out);
+// src [batch][n_in] -> dst [batch][n], any 64-bit words in, plain canonical words out; src may be dst when n_in == n
+int mod64_run(sh_ctx* c, const Mod64Call& mc, const uint64_t* tab, const void* src, uint64_t n_in, void* dst, uint32_t batch);
+
+// ---- api_mod64fri.hip -----------------------------------------------------------------------------------
+// FriBuffers with 8-byte values: the same workspace slots, the tree arenas as they are there
+struct Fri64Buffers {
+  uint64_t *vals, *next;
+  uint32_t *tree, *tree2, *ys;
+};
+int mod64fri_buffers(sh_ctx* c, uint64_t n, uint32_t batch, uint32_t samples, Fri64Buffers* b);
+// the commit rounds over mc's modulus on the plain canonical words in fb.vals (tab = mod64_table of the n-point forward transform); with
+// have_tree the tree of round 0 is already in fb.tree.  The FRI-only entries pass have_tree = false and stride = fri_proof_len.
+int mod64fri_rounds(sh_ctx* c, const Mod64Call& mc, const uint64_t* tab, Fri64Buffers fb, uint64_t n, uint64_t maxdeg_plus_1,
+                    uint32_t exclude, uint32_t samples, uint32_t batch, uint8_t* d_proof, uint64_t stride, bool have_tree);
+
 // ---- modverify.hip --------------------------------------------------------------------------------------
 // the host verifier behind sh_mod_fri_verify: serial, no context, no GPU
 int mod_fri_verify(const uint8_t modulus[32], const uint8_t* proof, uint64_t proof_len, const uint8_t merkle_root[32], uint64_t n,

@@ -264,3 +264,14 @@ hipError_t shk_n64_pointwise(const uint64_t* x, const uint64_t* y, uint64_t* out
 // words[i] = (8 x u32 limbs i) mod p; limbs[i] = words[i] zero-extended
 hipError_t shk_n64_from_limbs(const void* limbs, uint64_t* words, uint64_t count, const f64_mod& M, hipStream_t st);
 hipError_t shk_n64_to_limbs(const uint64_t* words, void* limbs, uint64_t count, hipStream_t st);
+
+// ---- mod64fri.hip: the FRI commit over any odd modulus below 2^64 on packed words (fri.py:189-266; mod64fri_items.cuh, which the two
+// files that use these include themselves: it brings blake2s.cuh) ----------------------------------------------------------------------
+struct M6Tree;
+struct M6Fold;
+struct M6Gather;
+// the leaf-kernel levels of the trees of t.values: nodes [n/4, n), and [n, 2n) when store_leaves; shk_merkle_upper_levels does the rest
+hipError_t shk_m6_leaves(const M6Tree& t, hipStream_t st);
+// a.column = the fold of a.values, one thread per row
+hipError_t shk_m6_fold(const M6Fold& a, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6_gather(const M6Gather& a, hipStream_t st);

@@ -9,12 +9,14 @@ proof back and `unpack_proof` rebuilds the reference's nested lists.
                                                       exclude_multiples_of=0, fri_spot_check_security_factor=40)
     prove_low_degree(...)  -- the upstream name of the same function (test_fri.py:170)
     SmoothSubgroupFRI(field).verify_proximity_proof(...) -- host-side verifier (fri.py:268-366)
+    mod64_prove_flat / mod64_fold -- the same commit over moduli below 2^64 on packed 64-bit words (sh_mod64_fri_prove)
     verify_flat / verify_flat_batch, mod_verify_flat / mod_verify_flat_batch -- the library's C and GPU verifiers on flat proofs
 """
 import ctypes
 
 from . import _lib
 from ._lib import MIMC_P
+from .fft import _words, _word_result
 from .merkle_tree import verify_branch, blake
 from .utils import get_pseudorandom_indices
 from .wireseq import WireList
@@ -83,6 +85,36 @@ def mod_prove_flat(modulus, coeff_bytes, n, root_of_unity, maxdeg_plus_1, exclud
                                      plen * batch)
     _lib.check(rc, "sh_mod_fri_prove")
     return out.raw
+
+
+def mod64_prove_flat(modulus, words, n, root_of_unity, maxdeg_plus_1, exclude_multiples_of=0, samples=40, batch=1):
+    """mod_prove_flat over any odd modulus below 2^64 on packed 64-bit words (sh_mod64_fri_prove): `words` = batch * n_coeffs native
+    8-byte words (the buffers fft.mod64_ntt takes: bytes, array('Q'), a numpy uint64 array, or a sequence of ints; any 64-bit values)
+    -> batch flat proofs, byte for byte mod_prove_flat's over the same modulus on the same values."""
+    src, _keep, count = _words(words)
+    if batch < 1 or count % batch:
+        raise ValueError("%d words are not %d vectors of equal length" % (count, batch))
+    plen = proof_len(n, maxdeg_plus_1, samples)
+    out = ctypes.create_string_buffer(plen * batch)
+    rc = _lib.lib().sh_mod64_fri_prove(_lib.ctx(), int(modulus), src, count // batch, n, int(root_of_unity), maxdeg_plus_1,
+                                       exclude_multiples_of, samples, batch, out, plen * batch)
+    _lib.check(rc, "sh_mod64_fri_prove")
+    return out.raw
+
+
+def mod64_fold(modulus, values, n, root_of_unity, special_x):
+    """One fold of n >= 4 words at the challenge special_x (an int below 2^256 or its 32 big-endian bytes; used modulo the modulus)
+    on the device (sh_mod64_fri_fold): `values` as in mod64_prove_flat -> the n / 4 canonical words of the column, a memoryview of
+    format 'Q' over a fresh bytearray."""
+    src, _keep, count = _words(values)
+    if count != n:
+        raise ValueError("%d words are not the %d values of the domain" % (count, n))
+    sx = bytes(special_x) if isinstance(special_x, (bytes, bytearray)) else int(special_x).to_bytes(32, "big")
+    out, dst = _word_result(n // 4)
+    rc = _lib.lib().sh_mod64_fri_fold(_lib.ctx(), int(modulus), src, n, int(root_of_unity), sx, dst)
+    _lib.check(rc, "sh_mod64_fri_fold")
+    del dst
+    return memoryview(out).cast("Q")
 
 
 def _field_modulus(coeffs, field):
