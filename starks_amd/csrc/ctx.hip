@@ -289,6 +289,7 @@ void sh_ctx_destroy(sh_ctx* c) {
   (void)trim(c);
   if (c->terms_dev) (void)hipFree(c->terms_dev);
   if (c->mod_terms_dev) (void)hipFree(c->mod_terms_dev);
+  if (c->mod64_terms_dev) (void)hipFree(c->mod64_terms_dev);
   if (c->bad_flag) (void)hipFree(c->bad_flag);
   for (int i = 0; i < 2; ++i) {
     if (c->pin[i]) (void)hipHostFree(c->pin[i]);

@@ -92,6 +92,11 @@ struct sh_ctx {
   std::vector<uint8_t> mod_terms_key;
   void* mod_terms_dev = nullptr;  // ModTermLayout
   uint32_t mod_terms_begin[SHK_STARK_MAX_WIDTH + 1] = {};
+  // the packed-word prover's term image (api_mod64stark.hip), a buffer of its own: packed and generic calls over one system alternate
+  // without re-uploading
+  std::vector<uint8_t> mod64_terms_key;
+  void* mod64_terms_dev = nullptr;  // Mod64TermLayout
+  uint32_t mod64_terms_begin[SHK_STARK_MAX_WIDTH + 1] = {};
   uint32_t* bad_flag = nullptr;  // [bad_cap] per-proof constraint flags of the calls since the last sh_stark_status*
   uint32_t bad_cap = 0;
 };
@@ -291,6 +296,18 @@ struct ModTermLayout {
 // the previous generic call's, prover or verifier: a prove -> verify pair over one system uploads once.  total = the sum of counts.
 int mod_stark_terms(sh_ctx* c, const fpm_mod& M, uint32_t width, const uint8_t* coefs, const uint8_t* exps, const uint32_t* counts,
                     uint64_t total);
+
+// ---- api_mod64stark.hip ---------------------------------------------------------------------------------
+// ModTermLayout on packed words (one allocation, ctx->mod64_terms_dev): Montgomery-form coefficient words, exponent rows of `width` bytes
+struct Mod64TermLayout {
+  static constexpr size_t MAXT = SHK_STARK_MAX_TERMS, MAXD = SHK_STARK_MAX_TERMS * SHK_STARK_MAX_WIDTH;
+  static constexpr size_t coef = 0;                                    // u64[MAXT]
+  static constexpr size_t dcoef = coef + MAXT * sizeof(uint64_t);      // u64[MAXD]
+  static constexpr size_t exps = dcoef + MAXD * sizeof(uint64_t);      // u8[MAXT][width]
+  static constexpr size_t dexps = exps + MAXT * SHK_STARK_MAX_WIDTH;   // u8[MAXD][width]
+  static constexpr size_t dbegin = (dexps + MAXD * SHK_STARK_MAX_WIDTH + 3) & ~(size_t)3;  // u32[W * W + 1]
+  static constexpr size_t total = dbegin + 4 * (SHK_STARK_MAX_WIDTH * SHK_STARK_MAX_WIDTH + 1);
+};
 
 // ---- api_stark.hip --------------------------------------------------------------------------------------
 // Device layout of the step-polynomial description (one allocation, ctx->terms_dev)

@@ -275,3 +275,20 @@ hipError_t shk_m6_leaves(const M6Tree& t, hipStream_t st);
 // a.column = the fold of a.values, one thread per row
 hipError_t shk_m6_fold(const M6Fold& a, const f64_mod& M, hipStream_t st);
 hipError_t shk_m6_gather(const M6Gather& a, hipStream_t st);
+
+// ---- mod64stark.hip: the STARK prover's middle over any prime modulus below 2^64 on packed words (stark.py:233-279;
+// mod64stark_items.cuh, which the two files that use these include themselves) ------------------------------------------------------------
+struct M6sArgs;
+struct M6sTables;
+struct M6sGather;
+// t.table = inv_z2 | fz | xpow of (p, steps, ext); t.den is [2][n] of scratch
+hipError_t shk_m6s_tables(const M6sTables& t, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6s_interp(const M6sArgs& a, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6s_qprep(const uint64_t* pcoef, uint64_t* q, uint64_t steps, uint64_t cols, const f64_mod& M, hipStream_t st);
+// D = C / Z and B = (P - I) / Z2 on the whole domain, then the packed-leaf Merkle tree over (P, D, B)
+hipError_t shk_m6s_quotients_and_merkelize(const M6sArgs& a, const f64_mod& M, uint32_t* d_nodes, hipStream_t st);
+// d_scal [batch][width][3]: alpha_j, alpha_j beta, alpha_j gamma in Montgomery form
+hipError_t shk_m6s_scalars(const uint32_t* d_mnodes, uint64_t tree_words, uint32_t width, uint32_t batch, uint64_t cpow, uint64_t* d_scal,
+                           const f64_mod& M, hipStream_t st);
+hipError_t shk_m6s_lincomb(const M6sArgs& a, const uint64_t* d_scal, uint64_t* d_l, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6s_gather(const M6sArgs& a, const M6sGather& ga, hipStream_t st);

@@ -315,6 +315,76 @@ def mod_prove_inputs_flat(modulus, input_bytes, steps, ext, width, step_polys, b
     return proofs.raw, outputs
 
 
+def mod64_prove_flat(modulus, witness_words, input_words, steps, ext, width, step_polys, batch=1, samples=SPOT_CHECKS):
+    """mod_prove_flat over any prime modulus below 2^64 on packed 64-bit words (sh_mod64_stark_prove): witness_words = batch * width *
+    steps and input_words = batch * width native 8-byte words (the buffers fft.mod64_ntt takes: bytes, array('Q'), a numpy uint64
+    array, or a sequence of ints; any 64-bit values, taken modulo `modulus`) -> batch flat proofs, byte for byte mod_prove_flat's over
+    the same modulus on the same values.  STARK.mk_proof does not route here: it keeps the 32-byte path for every modulus."""
+    from .fft import _words
+    wsrc, _wkeep, wcount = _words(witness_words)
+    isrc, _ikeep, icount = _words(input_words)
+    if wcount != batch * width * steps or icount != batch * width:
+        raise ValueError("witness must hold batch*width*steps and inputs batch*width 8-byte words "
+                         "(got %d and %d words for batch=%d, width=%d, steps=%d)" % (wcount, icount, batch, width, steps))
+    coefs, exps, counts, degree = pack_step_polys(step_polys, width, p=modulus)
+    plen = proof_len(steps, ext, width, degree, samples)
+    if plen == 0:
+        raise NotImplementedError("starks_amd.STARK: unsupported shape (steps=%d, ext=%d, width=%d, degree=%d)"
+                                  % (steps, ext, width, degree))
+    out = ctypes.create_string_buffer(plen * batch)
+    rc = _lib.lib().sh_mod64_stark_prove(_lib.ctx(), int(modulus), wsrc, isrc, steps, ext, width, coefs, exps, counts, samples, batch,
+                                         out, plen * batch)
+    if rc == -8:  # SH_ERR_CONSTRAINT: the reference's `assert cp % z == 0` (stark.py:76)
+        raise AssertionError("constraint polynomial is not a multiple of Z: the witness is not a valid trace")
+    _lib.check(rc, "sh_mod64_stark_prove")
+    return out.raw
+
+
+def mod64_prove_inputs_flat(modulus, input_bytes, steps, ext, width, step_polys, batch=1, samples=SPOT_CHECKS):
+    """mod_prove_inputs_flat with the packed-word prover: upload the inputs as little-endian limbs, then sh_dev_mod_stark_witness ->
+    sh_dev_mod64_from_limbs (witness and inputs) -> sh_dev_mod64_stark_prove -> sh_stark_status on device buffers (the witness never
+    leaves the device).  -> (batch flat proofs concatenated, outputs): outputs = witness[b][dim][-1] as [batch][width] wire form."""
+    if len(input_bytes) != 32 * batch * width:
+        raise ValueError("inputs must hold batch*width 32-byte elements (got %d bytes for batch=%d, width=%d)"
+                         % (len(input_bytes), batch, width))
+    coefs, exps, counts, degree = pack_step_polys(step_polys, width, p=modulus)
+    plen = proof_len(steps, ext, width, degree, samples)
+    if plen == 0:
+        raise NotImplementedError("starks_amd.STARK: unsupported shape (steps=%d, ext=%d, width=%d, degree=%d)"
+                                  % (steps, ext, width, degree))
+    L, ctx = _lib.lib(), _lib.ctx()
+    pb = int(modulus).to_bytes(32, "big")
+    raw_in = bytes(input_bytes)
+    limbs = b"".join(raw_in[i:i + 32][::-1] for i in range(0, len(raw_in), 32))  # wire form reversed = little-endian limbs
+    cols = batch * width
+    di, dw, dwi, dww, dp = (ctypes.c_void_p() for _ in range(5))
+    try:
+        for ptr, nbytes in ((di, 32 * cols), (dw, 32 * cols * steps), (dwi, 8 * cols), (dww, 8 * cols * steps), (dp, plen * batch)):
+            _lib.check(L.sh_dev_alloc(ctx, nbytes, ctypes.byref(ptr)), "sh_dev_alloc")
+        _lib.check(L.sh_dev_upload(ctx, limbs, di, len(limbs)), "sh_dev_upload")
+        _lib.check(L.sh_dev_mod_stark_witness(ctx, pb, di, steps, width, coefs, exps, counts, batch, dw), "sh_dev_mod_stark_witness")
+        _lib.check(L.sh_dev_mod64_from_limbs(ctx, int(modulus), dw, dww, cols * steps), "sh_dev_mod64_from_limbs")
+        _lib.check(L.sh_dev_mod64_from_limbs(ctx, int(modulus), di, dwi, cols), "sh_dev_mod64_from_limbs")
+        _lib.check(L.sh_dev_mod64_stark_prove(ctx, int(modulus), dww, dwi, steps, ext, width, coefs, exps, counts, samples, batch, dp),
+                   "sh_dev_mod64_stark_prove")
+        rc = L.sh_stark_status(ctx)
+        if rc == -8:  # a generated witness is a valid trace by construction: this would be a library fault
+            raise AssertionError("constraint polynomial is not a multiple of Z: the generated witness is not a valid trace")
+        _lib.check(rc, "sh_stark_status")
+        proofs = ctypes.create_string_buffer(plen * batch)
+        _lib.check(L.sh_dev_download(ctx, dp, proofs, plen * batch), "sh_dev_download")
+        last = ctypes.create_string_buffer(32 * cols)  # witness[b][dim][steps - 1], plain canonical limbs
+        _lib.check(L.sh_dev_download_2d(ctx, ctypes.c_void_p(dw.value + 32 * (steps - 1)), 32 * steps, last, 32, cols),
+                   "sh_dev_download_2d")
+    finally:
+        for ptr in (di, dw, dwi, dww, dp):
+            if ptr.value:
+                L.sh_dev_free(ctx, ptr)
+    raw = last.raw
+    outputs = b"".join(raw[i:i + 32][::-1] for i in range(0, len(raw), 32))
+    return proofs.raw, outputs
+
+
 class STARK(object):
     """Generates and verifies STARKs (stark.py:179-402); same constructor arguments."""
 
