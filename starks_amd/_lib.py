@@ -146,6 +146,8 @@ def lib():
         "sh_mod_stark_witness": (i32, [c_p, u8p, u8p, u64, u32, u8p, u8p, c_p, u32, c_p, u64]),
         "sh_mod64_stark_prove": (i32, [c_p, u64, c_p, c_p, u64, u32, u32, u8p, u8p, c_p, u32, u32, c_p, u64]),
         "sh_dev_mod64_stark_prove": (i32, [c_p, u64, c_p, c_p, u64, u32, u32, u8p, u8p, c_p, u32, u32, c_p]),
+        "sh_dev_mod64_stark_witness": (i32, [c_p, u64, c_p, u64, u32, u8p, u8p, c_p, u32, c_p]),
+        "sh_mod64_stark_witness": (i32, [c_p, u64, c_p, u64, u32, u8p, u8p, c_p, u32, c_p, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares

@@ -4,6 +4,8 @@
 // evaluations and the tree built here), the tree levels above the leaf kernels and the index sampler the MiMC path's (kernels.hip).
 // The proof bytes are sh_mod_stark_prove's over the same modulus on the same values.  Every check runs on the host before anything is
 // launched.
+// Also AIR.generate_witness on packed words over any odd modulus below 2^64 (sh_mod64_stark_witness, sh_dev_mod64_stark_witness:
+// mod64witness.hip launched in slices), through the same term image and key: generate -> prove over one system uploads once.
 #include "ctx.hpp"
 #include "mod64stark_items.cuh"
 using namespace shk;
@@ -224,6 +226,53 @@ int run_mod64_stark(sh_ctx* c, const Mod64StarkCall& sc, uint64_t* d_wit, const 
   return mod64fri_rounds(c, sc.fwd_n, tab_n, fb, n, steps * (uint64_t)sc.degree, ext, 40, batch,
                          d_proof + stark_header_len(n, width, samples), sc.stride, true);
 }
+
+// ---- AIR.generate_witness (air.py:32-52, 121-123) on packed words: mod64witness.hip, launched in slices of steps ------------------------
+// every host check of a witness call but the null pointers; on SH_OK M holds the modulus block and *total the number of terms
+int mod64_witness_check(sh_ctx* c, const char* who, uint64_t modulus, uint64_t steps, uint32_t width, const uint32_t* counts,
+                        uint32_t batch, f64_mod* M, uint64_t* total) {
+  if (!f64_mod_init(modulus, M)) return refuse(c, who, SH_ERR_INVALID, "the modulus must be odd and at least 3");
+  if (steps == 0 || width == 0 || batch == 0) return refuse(c, who, SH_ERR_INVALID, "steps, width and batch must be at least 1");
+  if (width > SHK_STARK_MAX_WIDTH) return refuse(c, who, SH_ERR_UNSUPPORTED, "width is limited to 9 (stark.py:106-126)");
+  *total = 0;
+  for (uint32_t d = 0; d < width; ++d) *total += counts[d];
+  if (*total == 0) return refuse(c, who, SH_ERR_INVALID, "the step polynomials have no terms");
+  if (*total > SHK_STARK_MAX_TERMS) return refuse(c, who, SH_ERR_UNSUPPORTED, "more step-polynomial terms than SHK_STARK_MAX_TERMS");
+  const uint64_t cols = (uint64_t)batch * width;
+  if (cols > 0xffffffffull || steps > (~0ull / 8) / cols)
+    return refuse(c, who, SH_ERR_UNSUPPORTED, "batch * width must be below 2^32 and the witness's byte count must fit 64 bits");
+  return SH_OK;
+}
+
+// d_wit [batch][width][steps], plain canonical words, from d_in [batch][width]; the terms are the ones mod64_stark_terms just uploaded.
+// The plan comes from the caller's term bytes: a coefficient counts as 1 when it is 1 modulo p, as the kernel derives it from the image.
+int run_mod64_witness(sh_ctx* c, const f64_mod& M, const uint64_t* d_in, uint64_t* d_wit, uint64_t steps, uint32_t width,
+                      const uint8_t* coefs, const uint8_t* exps, const uint32_t* counts, uint32_t batch) {
+  WiRow rows[SHK_STARK_MAX_TERMS];
+  uint32_t T = 0;
+  for (uint32_t d = 0; d < width; ++d)
+    for (uint32_t i = 0; i < counts[d]; ++i, ++T)
+      rows[T] = wi_pack_row(d, m6w_unit(f64_to_mont(m6s_from_wire(coefs + 32ull * T, M), M), M), exps + (size_t)T * width, width);
+  Mod64WitnessArgs a;
+  memset(&a, 0, sizeof a);
+  m6w_plan(rows, T, width, (uint32_t)shk_knobs().witness_group, (uint64_t)shk_knobs().witness_slice, &a.plan);
+  const bool inl = shk_knobs().witness_inline;
+  const uint8_t* tb = reinterpret_cast<const uint8_t*>(c->mod64_terms_dev);
+  a.inputs = d_in;
+  a.wit = d_wit;
+  a.steps = steps;
+  a.batch = batch;
+  a.nterms = T;
+  a.coef = reinterpret_cast<const uint64_t*>(tb + Mod64TermLayout::coef);
+  a.exps = tb + Mod64TermLayout::exps;
+  memcpy(a.begin, c->mod64_terms_begin, sizeof a.begin);
+  for (a.k0 = 0; a.k0 < steps; a.k0 = a.k1) {  // each dispatch resumes from the last row the previous one wrote
+    a.k1 = steps - a.k0 > a.plan.slice ? a.k0 + a.plan.slice : steps;
+    HIP_TRY(c, shk_mod64_witness_slice(a, M, width, inl, c->stream));
+  }
+  if (!inl) HIP_TRY(c, shk_mod64_witness_finish(d_wit, (uint64_t)batch * width * steps, M, c->stream));
+  return SH_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -267,5 +316,45 @@ int sh_mod64_stark_prove(sh_ctx* c, uint64_t modulus, const uint64_t* witness, c
   SH_TRY(run_mod64_stark(c, sc, dwit, dwit + wn, steps, ext, width, samples, batch, reinterpret_cast<uint8_t*>(dp)));
   SH_TRY(d2h(c, proof, dp, (size_t)sc.stride * batch));
   return sh_stark_status(c);
+}
+
+int sh_dev_mod64_stark_witness(sh_ctx* c, uint64_t modulus, const void* d_inputs, uint64_t steps, uint32_t width,
+                               const uint8_t* term_coefs, const uint8_t* term_exps, const uint32_t* term_counts, uint32_t batch,
+                               void* d_witness) {
+  const char* who = "sh_dev_mod64_stark_witness";
+  if (!c) return SH_ERR_INVALID;
+  if (!d_inputs || !term_coefs || !term_exps || !term_counts || !d_witness) return refuse(c, who, SH_ERR_INVALID, "null pointer");
+  f64_mod M;
+  uint64_t total = 0;
+  SH_TRY(mod64_witness_check(c, who, modulus, steps, width, term_counts, batch, &M, &total));
+  if (any_overlap(d_inputs, 8ull * batch * width, d_witness, 8ull * batch * width * steps))
+    return refuse(c, who, SH_ERR_INVALID, "d_inputs and d_witness overlap");
+  SH_TRY(enter(c));
+  SH_TRY(mod64_stark_terms(c, M, width, term_coefs, term_exps, term_counts, total));
+  return run_mod64_witness(c, M, reinterpret_cast<const uint64_t*>(d_inputs), reinterpret_cast<uint64_t*>(d_witness), steps, width,
+                           term_coefs, term_exps, term_counts, batch);
+}
+
+int sh_mod64_stark_witness(sh_ctx* c, uint64_t modulus, const uint64_t* inputs, uint64_t steps, uint32_t width, const uint8_t* term_coefs,
+                           const uint8_t* term_exps, const uint32_t* term_counts, uint32_t batch, uint64_t* witness,
+                           uint64_t witness_cap) {
+  const char* who = "sh_mod64_stark_witness";
+  if (!c) return SH_ERR_INVALID;
+  if (!inputs || !term_coefs || !term_exps || !term_counts || !witness) return refuse(c, who, SH_ERR_INVALID, "null pointer");
+  f64_mod M;
+  uint64_t total = 0;
+  SH_TRY(mod64_witness_check(c, who, modulus, steps, width, term_counts, batch, &M, &total));
+  const uint64_t cols = (uint64_t)batch * width, count = cols * steps;
+  if (witness_cap < count) return refuse(c, who, SH_ERR_TOO_SMALL, "witness_cap is below batch * width * steps words");
+  SH_TRY(enter(c));
+  SH_TRY(mod64_stark_terms(c, M, width, term_coefs, term_exps, term_counts, total));
+  // the words go up as they are: row 0 reduces an input at or above p on the device
+  void *in = nullptr, *w = nullptr;
+  SH_TRY(ws_get(c, sh_ctx::WS_Y, (size_t)cols * 8, &in));
+  SH_TRY(ws_get(c, sh_ctx::WS_ST_TRACE, (size_t)count * 8, &w));
+  SH_TRY(h2d(c, in, inputs, (size_t)cols * 8));
+  SH_TRY(run_mod64_witness(c, M, reinterpret_cast<const uint64_t*>(in), reinterpret_cast<uint64_t*>(w), steps, width, term_coefs,
+                           term_exps, term_counts, batch));
+  return d2h(c, witness, w, (size_t)count * 8);
 }
 }  // extern "C"

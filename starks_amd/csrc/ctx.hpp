@@ -16,12 +16,16 @@
 #include "verify_items.cuh"
 #include "witness_items.cuh"
 #include "modwitness_items.cuh"
+#include "mod64witness_items.cuh"
 
 // witness.hip
 hipError_t shk_stark_witness_slice(const WitnessArgs& a, uint32_t width, hipStream_t st);
 // modwitness.hip: rows [a.k0, a.k1) over M (inl: convert on the store path); the closing Montgomery -> plain pass of the default form
 hipError_t shk_mod_witness_slice(const ModWitnessArgs& a, const fpm_mod& M, uint32_t width, bool inl, hipStream_t st);
 hipError_t shk_mod_witness_finish(fpm* wit, uint64_t count, const fpm_mod& M, hipStream_t st);
+// mod64witness.hip: their twins on packed 64-bit words
+hipError_t shk_mod64_witness_slice(const Mod64WitnessArgs& a, const f64_mod& M, uint32_t width, bool inl, hipStream_t st);
+hipError_t shk_mod64_witness_finish(uint64_t* wit, uint64_t count, const f64_mod& M, hipStream_t st);
 // verify_dev.hip
 hipError_t shk_verify_batch(const VbPlan& p, const uint8_t* proofs, uint32_t batch, const uint8_t* roots, const fp* inputs,
                             const fp* outputs, uint64_t io_stride, const fp* coef, const uint8_t* exps, uint32_t row,

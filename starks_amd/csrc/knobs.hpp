@@ -18,9 +18,11 @@
 //                                  (ntt_narrow_pass_kernel; default 256 = the CUs of the chip; 0 = never)
 //   STARKHIP_WITNESS_GROUP=1|2|4|8|16  lanes per unit of the witness generator (witness.hip; default: chosen from the term table)
 //   STARKHIP_WITNESS_SLICE=k       steps per witness dispatch (default: about 2^13 sequential products per dispatch, at least 1)
-//                                  (over another modulus, modwitness.hip: about 2^12, modwitness_items.cuh).  Both apply to both paths
-//   STARKHIP_WITNESS_STORE=pass|inline  how the generic witness generator reaches plain form: one closing pass over the witness
-//                                  (default), or a conversion on the kernel's store path (modwitness_items.cuh; tools/mod_witness_time.py)
+//                                  (over another modulus, modwitness.hip: about 2^12, modwitness_items.cuh; on packed 64-bit words,
+//                                  mod64witness.hip: about 2^14, mod64witness_items.cuh).  Both apply to all three paths
+//   STARKHIP_WITNESS_STORE=pass|inline  how the generic and the packed-word witness generator reach plain form: one closing pass over
+//                                  the witness (default), or a conversion on the kernel's store path (modwitness_items.cuh,
+//                                  mod64witness_items.cuh; tools/mod_witness_time.py, tools/mod64_witness_time.py)
 //   STARKHIP_EVAL_PATH=direct|tree  the path of every sh_poly_eval call (default: chosen per call, poly_items.cuh:pe_direct_preferred)
 //   STARKHIP_MODNTT_TILE_LOG=2..10 elements per tile (log2) of the generic transform (modntt_items.cuh; default 10): small values force
 //                                  plans of many passes at small n (tests/test_gpu_modntt.py)

@@ -385,6 +385,63 @@ def mod64_prove_inputs_flat(modulus, input_bytes, steps, ext, width, step_polys,
     return proofs.raw, outputs
 
 
+def mod64_witness_flat(modulus, input_words, steps, width, step_polys, batch=1):
+    """mod_witness_flat on packed 64-bit words over any odd modulus 3 <= p < 2^64, composite ones included (sh_mod64_stark_witness):
+    input_words = batch * width native 8-byte words (the buffers fft.mod64_ntt takes; any 64-bit values, taken modulo `modulus`) -> the
+    witness [batch][width][steps] as bytes of native words, plain and canonical: what mod64_prove_flat takes.  Any steps >= 1."""
+    from .fft import _words
+    isrc, _ikeep, icount = _words(input_words)
+    if icount != batch * width:
+        raise ValueError("inputs must hold batch*width 8-byte words (got %d words for batch=%d, width=%d)" % (icount, batch, width))
+    coefs, exps, counts, _ = pack_step_polys(step_polys, width, p=modulus)
+    count = batch * width * steps
+    out = ctypes.create_string_buffer(8 * count)
+    _lib.check(_lib.lib().sh_mod64_stark_witness(_lib.ctx(), int(modulus), isrc, steps, width, coefs, exps, counts, batch, out, count),
+               "sh_mod64_stark_witness")
+    return out.raw
+
+
+def mod64_prove_input_words_flat(modulus, input_words, steps, ext, width, step_polys, batch=1, samples=SPOT_CHECKS):
+    """mod64_prove_inputs_flat from words, on words throughout: upload the inputs, then sh_dev_mod64_stark_witness ->
+    sh_dev_mod64_stark_prove -> sh_stark_status on device buffers (the witness never leaves the device, and no 32-byte copy of it
+    exists).  -> (batch flat proofs concatenated, output_words): output_words = witness[b][dim][steps - 1] as [batch][width] native
+    words."""
+    from .fft import _words
+    isrc, _ikeep, icount = _words(input_words)
+    cols = batch * width
+    if icount != cols:
+        raise ValueError("inputs must hold batch*width 8-byte words (got %d words for batch=%d, width=%d)" % (icount, batch, width))
+    coefs, exps, counts, degree = pack_step_polys(step_polys, width, p=modulus)
+    plen = proof_len(steps, ext, width, degree, samples)
+    if plen == 0:
+        raise NotImplementedError("starks_amd.STARK: unsupported shape (steps=%d, ext=%d, width=%d, degree=%d)"
+                                  % (steps, ext, width, degree))
+    L, ctx = _lib.lib(), _lib.ctx()
+    raw_in = isrc if isinstance(isrc, bytes) else bytes(isrc)
+    di, dw, dp = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    try:
+        for ptr, nbytes in ((di, 8 * cols), (dw, 8 * cols * steps), (dp, plen * batch)):
+            _lib.check(L.sh_dev_alloc(ctx, nbytes, ctypes.byref(ptr)), "sh_dev_alloc")
+        _lib.check(L.sh_dev_upload(ctx, raw_in, di, len(raw_in)), "sh_dev_upload")
+        _lib.check(L.sh_dev_mod64_stark_witness(ctx, int(modulus), di, steps, width, coefs, exps, counts, batch, dw),
+                   "sh_dev_mod64_stark_witness")
+        _lib.check(L.sh_dev_mod64_stark_prove(ctx, int(modulus), dw, di, steps, ext, width, coefs, exps, counts, samples, batch, dp),
+                   "sh_dev_mod64_stark_prove")
+        rc = L.sh_stark_status(ctx)
+        if rc == -8:  # a generated witness is a valid trace by construction: this would be a library fault
+            raise AssertionError("constraint polynomial is not a multiple of Z: the generated witness is not a valid trace")
+        _lib.check(rc, "sh_stark_status")
+        proofs = ctypes.create_string_buffer(plen * batch)
+        _lib.check(L.sh_dev_download(ctx, dp, proofs, plen * batch), "sh_dev_download")
+        last = ctypes.create_string_buffer(8 * cols)  # witness[b][dim][steps - 1], plain canonical words
+        _lib.check(L.sh_dev_download_2d(ctx, ctypes.c_void_p(dw.value + 8 * (steps - 1)), 8 * steps, last, 8, cols), "sh_dev_download_2d")
+    finally:
+        for ptr in (di, dw, dp):
+            if ptr.value:
+                L.sh_dev_free(ctx, ptr)
+    return proofs.raw, last.raw
+
+
 class STARK(object):
     """Generates and verifies STARKs (stark.py:179-402); same constructor arguments."""
 
