@@ -148,6 +148,19 @@ def lib():
         "sh_dev_mod64_stark_prove": (i32, [c_p, u64, c_p, c_p, u64, u32, u32, u8p, u8p, c_p, u32, u32, c_p]),
         "sh_dev_mod64_stark_witness": (i32, [c_p, u64, c_p, u64, u32, u8p, u8p, c_p, u32, c_p]),
         "sh_mod64_stark_witness": (i32, [c_p, u64, c_p, u64, u32, u8p, u8p, c_p, u32, c_p, u64]),
+        "sh_mod_poly_max_transform": (u64, [i32, u64, u64]),
+        "sh_dev_mod_multi_inv": (i32, [c_p, u8p, c_p, c_p, u64]),
+        "sh_mod_multi_inv": (i32, [c_p, u8p, u8p, u64, c_p]),
+        "sh_dev_mod_multi_interp_4": (i32, [c_p, u8p, c_p, c_p, u64, c_p]),
+        "sh_mod_multi_interp_4": (i32, [c_p, u8p, u8p, u8p, u64, c_p]),
+        "sh_dev_mod_poly_mul": (i32, [c_p, u8p, u8p, u32, c_p, u64, c_p, u64, c_p]),
+        "sh_mod_poly_mul": (i32, [c_p, u8p, u8p, u32, u8p, u64, u8p, u64, c_p]),
+        "sh_dev_mod_poly_divmod": (i32, [c_p, u8p, u8p, u32, c_p, u64, c_p, u64, c_p, c_p]),
+        "sh_mod_poly_divmod": (i32, [c_p, u8p, u8p, u32, u8p, u64, u8p, u64, c_p, c_p]),
+        "sh_dev_mod_zpoly": (i32, [c_p, u8p, u8p, u32, c_p, u64, c_p]),
+        "sh_mod_zpoly": (i32, [c_p, u8p, u8p, u32, u8p, u64, c_p]),
+        "sh_dev_mod_lagrange_interp": (i32, [c_p, u8p, u8p, u32, c_p, c_p, u64, c_p]),
+        "sh_mod_lagrange_interp": (i32, [c_p, u8p, u8p, u32, u8p, u8p, u64, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares
@@ -289,3 +302,85 @@ def order_of_root(root, modulus=MIMC_P):
         t = t * t % modulus
         n *= 2
     return None
+
+
+# ---- roots of unity and primality for the polynomial entries over a run-time modulus (sh_mod_poly_*) ----------------------------------
+MOD_POLY_MUL, MOD_POLY_DIVMOD, MOD_POLY_ZPOLY, MOD_POLY_LAGRANGE = 0, 1, 2, 3  # sh_mod_poly_max_transform's op
+MAX_ROOT_LOG = 26  # the generic transform's largest size
+_two_adic = {}
+_prime = {}
+_MR_BASES = (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37, 41)
+
+
+def is_probable_prime(p):
+    """Miller-Rabin on fixed bases, cached per p.  It guards ROUTING (a composite modulus must keep the host path, where the
+    reference's algorithms are defined for it), not a correctness claim: the device entries take the caller's word for primality."""
+    p = int(p)
+    hit = _prime.get(p)
+    if hit is not None:
+        return hit
+    if p < 2:
+        res = False
+    elif p in _MR_BASES:
+        res = True
+    elif any(p % b == 0 for b in _MR_BASES):
+        res = False
+    else:
+        d, s = p - 1, 0
+        while d % 2 == 0:
+            d, s = d // 2, s + 1
+        res = True
+        for a in _MR_BASES:
+            x = pow(a, d, p)
+            if x in (1, p - 1):
+                continue
+            for _ in range(s - 1):
+                x = x * x % p
+                if x == p - 1:
+                    break
+            else:
+                res = False
+                break
+    _prime[p] = res
+    return res
+
+
+def two_adic_root(p):
+    """(root, k) for an odd prime p: a root of unity of order exactly 2^k, k = min(v2(p - 1), 26), as the sh_mod_poly_* entries take
+    it -- g^((p - 1) >> k) for the smallest g >= 2 with g^((p - 1) / 2) = -1 (a quadratic non-residue, so the power has the full
+    order).  Cached per p.  Any root of that order gives the same results: they are exact polynomial identities."""
+    p = int(p)
+    hit = _two_adic.get(p)
+    if hit is None:
+        if p < 3 or p % 2 == 0:
+            raise ValueError("two_adic_root needs an odd prime")
+        s = ((p - 1) & -(p - 1)).bit_length() - 1
+        g = 2
+        while pow(g, (p - 1) // 2, p) != p - 1:
+            g += 1
+            if g > 1000:
+                raise ValueError("no quadratic non-residue below 1000: %d is not prime" % p)
+        k = min(s, MAX_ROOT_LOG)
+        hit = _two_adic[p] = (pow(g, (p - 1) >> k, p), k)
+    return hit
+
+
+def mod_poly_args(modulus, root=None):
+    """(modulus bytes, root bytes, root_log) of a sh_mod_poly_* call; root = None: two_adic_root(modulus), else (root, root_log)"""
+    m = int(modulus)
+    w, k = two_adic_root(m) if root is None else root
+    return m.to_bytes(32, "big"), (int(w) % m).to_bytes(32, "big"), int(k)
+
+
+def mod_poly_routable(p, op, n_a, n_b=0):
+    """The field half of the routing rule of Polynomial and poly_utils over IntegersModP(p), p not the MiMC prime: this process
+    already holds a context (read as an attribute: the rule never creates one and never loads the library), p is odd, below 2^256
+    and passes the prime test, and the call's largest transform (sh_mod_poly_max_transform) fits the field's 2-adicity."""
+    if _ctx is None:
+        return False
+    p = int(p)
+    if p == MIMC_P or p < 3 or p % 2 == 0 or p >> 256 or not is_probable_prime(p):
+        return False
+    if op is None:  # multi_inv, multi_interp_4: no transform
+        return True
+    return lib().sh_mod_poly_max_transform(op, n_a, n_b) <= 1 << two_adic_root(p)[1]

@@ -1,0 +1,374 @@
+// api_modpoly.hip -- polynomial products, division, zpoly, lagrange_interp, batch inversion and four-point interpolation over any prime
+// modulus below 2^256 on the host side: the drivers of poly_items.cuh over the generic transform (api_modntt.hip: mod_table, mod_run)
+// and the kernels of modpoly.hip.  Every check runs here before the first launch; every error text opens with the entry's name.
+#include "ctx.hpp"
+#include "modpoly_items.cuh"
+using namespace shk;
+
+namespace {
+constexpr uint64_t MP_MAX_ITEMS = 1ull << 52;    // keeps every byte count of a call far from 2^64
+constexpr uint64_t MP_MAX_PRODUCT = 1ull << 25;  // the MiMC entries' limits (api_poly.hip)
+constexpr uint64_t MP_MAX_DIVIDEND = 1ull << 24;
+constexpr uint64_t MP_MAX_POINTS = 1ull << 20;
+constexpr int MP_MAX_ROOT_LOG = 26;  // MN_MAX_LOG_N
+
+int fail(sh_ctx* c, const char* who, const std::string& what, int code) {
+  c->err = std::string(who) + ": " + what;
+  return code;
+}
+int check_modulus(sh_ctx* c, const char* who, const uint8_t* modulus, fpm_mod* M) {
+  if (!modulus) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (!fpm_mod_init(modulus, M)) return fail(c, who, "the modulus must be odd and at least 3", SH_ERR_INVALID);
+  return SH_OK;
+}
+
+// everything a call derives from (modulus, root, root_log) on the host, and the back end of poly_items.cuh's drivers over it
+struct ModOps {
+  sh_ctx* c;
+  fpm_mod M;
+  fpm root_mont;  // the caller's root of order 2^root_log, Montgomery form
+  int root_log;
+  ModCall call[2][MP_MAX_ROOT_LOG + 1];  // [inverse][log2 n], filled on first use
+  bool have[2][MP_MAX_ROOT_LOG + 1];
+
+  // modulus, root below p, root of order exactly 2^root_log
+  int init(sh_ctx* ctx, const char* who, const uint8_t* modulus, const uint8_t* root, uint32_t rl) {
+    c = ctx;
+    memset(have, 0, sizeof have);
+    SH_TRY(check_modulus(c, who, modulus, &M));
+    if (!root) return fail(c, who, "null pointer", SH_ERR_INVALID);
+    if (rl > (uint32_t)MP_MAX_ROOT_LOG) return fail(c, who, "root_log is limited to 26", SH_ERR_UNSUPPORTED);
+    const fpm w = fpm_from_wire_bytes(root);
+    if (!fpm_below_p(w, M)) return fail(c, who, "root is not below the modulus", SH_ERR_ROOT_ORDER);
+    if (!mn_check_root(w, 1ull << rl, M)) return fail(c, who, "root does not have order 2^root_log in this field", SH_ERR_ROOT_ORDER);
+    root_log = (int)rl;
+    root_mont = fpm_to_mont(w, M);
+    return SH_OK;
+  }
+  // the largest transform of the call against the root's order
+  int fits(const char* who, uint64_t need) const {
+    if (need <= (1ull << root_log)) return SH_OK;
+    return fail(c, who,
+                "the call needs a transform of size " + std::to_string(need) + " and the root given has order " +
+                    std::to_string(1ull << root_log),
+                SH_ERR_ROOT_ORDER);
+  }
+  const ModCall& get(int k, bool inverse) {
+    ModCall& mc = call[inverse][k];
+    if (!have[inverse][k]) {
+      mc.M = M;
+      mc.log_n = k;
+      fpm w = root_mont;  // root^(2^(root_log - k)): order 2^k
+      for (int i = k; i < root_log; ++i) w = fpm_mul(w, w, M);
+      mc.root_mont = inverse ? fpm_pow(w, (1ull << k) - 1, M) : w;
+      mc.scale = inverse ? mn_inv_n(k, M) : fpm_from_u32(1u);
+      have[inverse][k] = true;
+    }
+    return mc;
+  }
+
+  int ntt(const fpm* src, fpm* dst, uint64_t batch, uint64_t n, uint64_t n_in, bool inverse) {
+    const int k = ilog2(n);
+    if (k > root_log) return fail(c, "generic polynomial arithmetic", "transform above the root's order", SH_ERR_ROOT_ORDER);
+    const ModCall& mc = get(k, inverse);
+    const fpm* tw = nullptr;
+    SH_TRY(mod_table(c, mc, &tw));
+    const uint64_t ni = n_in ? n_in : n, per = (1ull << MN_MAX_LOG_N) >> k;  // a level above batch n = 2^26 runs as several calls
+    for (uint64_t b0 = 0; b0 < batch; b0 += per) {
+      const uint64_t nb = batch - b0 < per ? batch - b0 : per;
+      SH_TRY(mod_run(c, mc, tw, src + b0 * ni, ni, dst + b0 * n, (uint32_t)nb, false, false));
+    }
+    return SH_OK;
+  }
+  int copy(const PaCopy& k, const fpm* src, fpm* dst) { HIP_TRY(c, shk_mp_copy(k, src, dst, M, c->stream)); return SH_OK; }
+  int pointwise(const fpm* a, const fpm* b, fpm* out, uint64_t n) { HIP_TRY(c, shk_mn_pointwise(a, b, out, n, M, c->stream)); return SH_OK; }
+  int tree(const fpm* hz, fpm* oz, const fpm* hn, fpm* on, uint32_t log2d, uint64_t nodes) {
+    HIP_TRY(c, shk_mp_tree(hz, oz, hn, on, log2d, nodes, M, c->stream));
+    return SH_OK;
+  }
+  int mid(const fpm* hd, fpm* hr, uint32_t log2d, uint64_t children) { HIP_TRY(c, shk_mp_mid(hd, hr, log2d, children, M, c->stream)); return SH_OK; }
+  int newton(const fpm* F, fpm* G, uint64_t n) { HIP_TRY(c, shk_mp_newton(F, G, n, M, c->stream)); return SH_OK; }
+  int inv1(const fpm* src, fpm* dst) { HIP_TRY(c, shk_mp_inv1(src, dst, M, c->stream)); return SH_OK; }
+  int deriv_rev(const fpm* top, fpm* out, uint64_t N, uint64_t n) { HIP_TRY(c, shk_mp_deriv_rev(top, out, N, n, M, c->stream)); return SH_OK; }
+  int multi_inv(const fpm* in, fpm* out, uint64_t n) {
+    void* s = nullptr;
+    SH_TRY(ws_get(c, sh_ctx::WS_INV, (size_t)shk_mp_multi_inv_scratch(n) * sizeof(fpm), &s));
+    HIP_TRY(c, shk_mp_multi_inv(in, out, n, static_cast<fpm*>(s), M, c->stream));
+    return SH_OK;
+  }
+  int multi_interp_4(const fpm* xs, const fpm* ys, fpm* coeffs, uint64_t rows) {
+    void* s = nullptr;
+    SH_TRY(ws_get(c, sh_ctx::WS_INV, (size_t)shk_mp_multi_interp_4_scratch(rows) * sizeof(fpm), &s));
+    HIP_TRY(c, shk_mp_multi_interp_4(xs, ys, coeffs, rows, static_cast<fpm*>(s), M, c->stream));
+    return SH_OK;
+  }
+  int weights(const fpm* ys, const fpm* inv, fpm* out, uint64_t n, uint64_t N) {
+    HIP_TRY(c, shk_mp_weights(ys, inv, out, n, N, M, c->stream));
+    return SH_OK;
+  }
+  int sub(const fpm* a, const fpm* b, fpm* out, uint64_t n) { HIP_TRY(c, shk_mp_sub(a, b, out, n, M, c->stream)); return SH_OK; }
+  int buf(int slot, uint64_t elems, fpm** out) { return ws(sh_ctx::WS_PA_TREE + slot, elems, out); }
+  int ws(int slot, uint64_t elems, fpm** out) {
+    void* p = nullptr;
+    SH_TRY(ws_get(c, slot, (size_t)elems * sizeof(fpm), &p));
+    *out = static_cast<fpm*>(p);
+    return SH_OK;
+  }
+  // host-buffer forms: n wire values into a workspace as limbs / limbs out as wire values; nothing is reduced
+  int upload(const uint8_t* in, uint64_t n, int slot, fpm** out) {
+    SH_TRY(ws(slot, n, out));
+    SH_TRY(h2d(c, *out, in, (size_t)n * 32));
+    HIP_TRY(c, shk_mp_swap(*out, *out, n, c->stream));
+    return SH_OK;
+  }
+  int download(fpm* d, uint8_t* out, uint64_t n) {
+    HIP_TRY(c, shk_mp_swap(d, d, n, c->stream));
+    return d2h(c, out, d, (size_t)n * 32);
+  }
+};
+
+// the divisor's leading coefficient, reduced: zero mod p ?
+bool lc_is_zero(const fpm& lc, const fpm_mod& M) { return fpm_is_zero(fpm_canon(lc, M)); }
+
+// the size checks shared by the two forms of an entry; *need = the largest transform
+int mul_sizes(sh_ctx* c, const char* who, uint64_t n_a, uint64_t n_b) {
+  if (n_a > MP_MAX_PRODUCT || n_b > MP_MAX_PRODUCT || (n_a && n_b && n_a + n_b - 1 > MP_MAX_PRODUCT))
+    return fail(c, who, "the product is limited to 2^25 coefficients", SH_ERR_INVALID);
+  return SH_OK;
+}
+int divmod_sizes(sh_ctx* c, const char* who, uint64_t n_a, uint64_t n_b) {
+  if (n_b == 0) return fail(c, who, "the divisor is empty", SH_ERR_INVALID);
+  if (n_a > MP_MAX_DIVIDEND || n_b > MP_MAX_DIVIDEND) return fail(c, who, "dividend and divisor are limited to 2^24 coefficients", SH_ERR_INVALID);
+  return SH_OK;
+}
+int point_sizes(sh_ctx* c, const char* who, uint64_t n) {
+  if (n > MP_MAX_POINTS) return fail(c, who, "the points are limited to 2^20", SH_ERR_INVALID);
+  return SH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+uint64_t sh_mod_poly_max_transform(int op, uint64_t n_a, uint64_t n_b) { return mp_max_transform(op, n_a, n_b); }
+
+int sh_dev_mod_multi_inv(sh_ctx* c, const uint8_t modulus[32], const void* d_in, void* d_out, uint64_t n) {
+  static const char who[] = "sh_dev_mod_multi_inv";
+  if (!c) return SH_ERR_INVALID;
+  if (!d_in || !d_out || !modulus) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (n > MP_MAX_ITEMS) return fail(c, who, "too many values", SH_ERR_INVALID);
+  if (partial_overlap(d_in, 32 * n, d_out, 32 * n)) return fail(c, who, "the buffers overlap in part", SH_ERR_INVALID);
+  ModOps o;
+  o.c = c;
+  SH_TRY(check_modulus(c, who, modulus, &o.M));
+  if (n == 0) return SH_OK;
+  SH_TRY(enter(c));
+  return o.multi_inv(static_cast<const fpm*>(d_in), static_cast<fpm*>(d_out), n);
+}
+
+int sh_mod_multi_inv(sh_ctx* c, const uint8_t modulus[32], const uint8_t* in, uint64_t n, uint8_t* out) {
+  static const char who[] = "sh_mod_multi_inv";
+  if (!c) return SH_ERR_INVALID;
+  if (!in || !out || !modulus) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (n > MP_MAX_ITEMS) return fail(c, who, "too many values", SH_ERR_INVALID);
+  ModOps o;
+  o.c = c;
+  SH_TRY(check_modulus(c, who, modulus, &o.M));
+  if (n == 0) return SH_OK;
+  SH_TRY(enter(c));
+  fpm* x = nullptr;
+  SH_TRY(o.upload(in, n, sh_ctx::WS_X, &x));
+  SH_TRY(o.multi_inv(x, x, n));
+  return o.download(x, out, n);
+}
+
+int sh_dev_mod_multi_interp_4(sh_ctx* c, const uint8_t modulus[32], const void* d_xs, const void* d_ys, uint64_t rows, void* d_coeffs) {
+  static const char who[] = "sh_dev_mod_multi_interp_4";
+  if (!c) return SH_ERR_INVALID;
+  if (!d_xs || !d_ys || !d_coeffs || !modulus) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (rows > MP_MAX_ITEMS) return fail(c, who, "too many rows", SH_ERR_INVALID);
+  const uint64_t bytes = 128 * rows;
+  if (partial_overlap(d_xs, bytes, d_coeffs, bytes) || partial_overlap(d_ys, bytes, d_coeffs, bytes))
+    return fail(c, who, "the buffers overlap in part", SH_ERR_INVALID);
+  ModOps o;
+  o.c = c;
+  SH_TRY(check_modulus(c, who, modulus, &o.M));
+  if (rows == 0) return SH_OK;
+  SH_TRY(enter(c));
+  return o.multi_interp_4(static_cast<const fpm*>(d_xs), static_cast<const fpm*>(d_ys), static_cast<fpm*>(d_coeffs), rows);
+}
+
+int sh_mod_multi_interp_4(sh_ctx* c, const uint8_t modulus[32], const uint8_t* xs, const uint8_t* ys, uint64_t rows, uint8_t* coeffs) {
+  static const char who[] = "sh_mod_multi_interp_4";
+  if (!c) return SH_ERR_INVALID;
+  if (!xs || !ys || !coeffs || !modulus) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (rows > MP_MAX_ITEMS) return fail(c, who, "too many rows", SH_ERR_INVALID);
+  ModOps o;
+  o.c = c;
+  SH_TRY(check_modulus(c, who, modulus, &o.M));
+  if (rows == 0) return SH_OK;
+  SH_TRY(enter(c));
+  fpm *x = nullptr, *y = nullptr;
+  SH_TRY(o.upload(xs, 4 * rows, sh_ctx::WS_X, &x));
+  SH_TRY(o.upload(ys, 4 * rows, sh_ctx::WS_Y, &y));
+  SH_TRY(o.multi_interp_4(x, y, x, rows));
+  return o.download(x, coeffs, 4 * rows);
+}
+
+int sh_dev_mod_poly_mul(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const void* d_a, uint64_t n_a,
+                        const void* d_b, uint64_t n_b, void* d_out) {
+  static const char who[] = "sh_dev_mod_poly_mul";
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(mul_sizes(c, who, n_a, n_b));
+  const uint64_t nc = n_a && n_b ? n_a + n_b - 1 : 0;
+  if (nc && (!d_a || !d_b || !d_out)) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (any_overlap(d_out, 32 * nc, d_a, 32 * n_a) || any_overlap(d_out, 32 * nc, d_b, 32 * n_b))
+    return fail(c, who, "the output overlaps an input", SH_ERR_INVALID);
+  ModOps o;
+  SH_TRY(o.init(c, who, modulus, root, root_log));
+  SH_TRY(o.fits(who, mp_max_transform(MP_OP_MUL, n_a, n_b)));
+  if (nc == 0) return SH_OK;
+  SH_TRY(enter(c));
+  fpm *t1, *t2;
+  SH_TRY(o.buf(PA_BUF_1, pa_pow2_at_least(nc), &t1));
+  SH_TRY(o.buf(PA_BUF_2, pa_pow2_at_least(nc), &t2));
+  return pa_mul(o, static_cast<const fpm*>(d_a), n_a, static_cast<const fpm*>(d_b), n_b, static_cast<fpm*>(d_out), t1, t2);
+}
+
+int sh_mod_poly_mul(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const uint8_t* a, uint64_t n_a,
+                    const uint8_t* b, uint64_t n_b, uint8_t* out) {
+  static const char who[] = "sh_mod_poly_mul";
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(mul_sizes(c, who, n_a, n_b));
+  const uint64_t nc = n_a && n_b ? n_a + n_b - 1 : 0;
+  if (nc && (!a || !b || !out)) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  ModOps o;
+  SH_TRY(o.init(c, who, modulus, root, root_log));
+  SH_TRY(o.fits(who, mp_max_transform(MP_OP_MUL, n_a, n_b)));
+  if (nc == 0) return SH_OK;
+  SH_TRY(enter(c));
+  fpm *x, *y, *d_out, *t1, *t2;
+  SH_TRY(o.upload(a, n_a, sh_ctx::WS_X, &x));
+  SH_TRY(o.upload(b, n_b, sh_ctx::WS_Y, &y));
+  SH_TRY(o.buf(PA_BUF_4, nc, &d_out));
+  SH_TRY(o.buf(PA_BUF_1, pa_pow2_at_least(nc), &t1));
+  SH_TRY(o.buf(PA_BUF_2, pa_pow2_at_least(nc), &t2));
+  SH_TRY(pa_mul(o, x, n_a, y, n_b, d_out, t1, t2));
+  return o.download(d_out, out, nc);
+}
+
+int sh_dev_mod_poly_divmod(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const void* d_a, uint64_t n_a,
+                           const void* d_b, uint64_t n_b, void* d_q, void* d_r) {
+  static const char who[] = "sh_dev_mod_poly_divmod";
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(divmod_sizes(c, who, n_a, n_b));
+  const uint64_t nq = n_a >= n_b ? n_a - n_b + 1 : 0, nr = n_a < n_b - 1 ? n_a : n_b - 1;
+  if (!d_b || (n_a && !d_a) || (nq && !d_q) || (nr && !d_r)) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  const void* in[2] = {d_a, d_b};
+  const uint64_t in_n[2] = {n_a, n_b};
+  for (int k = 0; k < 2; ++k)
+    if (any_overlap(d_q, 32 * nq, in[k], 32 * in_n[k]) || any_overlap(d_r, 32 * nr, in[k], 32 * in_n[k]))
+      return fail(c, who, "an output overlaps an input", SH_ERR_INVALID);
+  if (any_overlap(d_q, 32 * nq, d_r, 32 * nr)) return fail(c, who, "the outputs overlap", SH_ERR_INVALID);
+  ModOps o;
+  SH_TRY(o.init(c, who, modulus, root, root_log));
+  SH_TRY(o.fits(who, mp_max_transform(MP_OP_DIVMOD, n_a, n_b)));
+  SH_TRY(enter(c));
+  fpm lc;  // the one read-back: the divisor's leading coefficient, behind the work already queued on the stream
+  HIP_TRY(c, hipMemcpyAsync(&lc, static_cast<const fpm*>(d_b) + (n_b - 1), sizeof(fpm), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (lc_is_zero(lc, o.M)) return fail(c, who, "the divisor's leading coefficient is zero mod p", SH_ERR_INVALID);
+  if (n_a == 0) return SH_OK;
+  return pa_divmod(o, static_cast<const fpm*>(d_a), n_a, static_cast<const fpm*>(d_b), n_b, static_cast<fpm*>(d_q), static_cast<fpm*>(d_r));
+}
+
+int sh_mod_poly_divmod(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const uint8_t* a, uint64_t n_a,
+                       const uint8_t* b, uint64_t n_b, uint8_t* q, uint8_t* r) {
+  static const char who[] = "sh_mod_poly_divmod";
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(divmod_sizes(c, who, n_a, n_b));
+  const uint64_t nq = n_a >= n_b ? n_a - n_b + 1 : 0, nr = n_a < n_b - 1 ? n_a : n_b - 1;
+  if (!b || (n_a && !a) || (nq && !q) || (nr && !r)) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  ModOps o;
+  SH_TRY(o.init(c, who, modulus, root, root_log));
+  SH_TRY(o.fits(who, mp_max_transform(MP_OP_DIVMOD, n_a, n_b)));
+  if (lc_is_zero(fpm_from_wire_bytes(b + 32 * (n_b - 1)), o.M))
+    return fail(c, who, "the divisor's leading coefficient is zero mod p", SH_ERR_INVALID);
+  if (n_a == 0) return SH_OK;
+  SH_TRY(enter(c));
+  fpm *x, *y, *oq, *orr;
+  SH_TRY(o.upload(a, n_a, sh_ctx::WS_X, &x));
+  SH_TRY(o.upload(b, n_b, sh_ctx::WS_Y, &y));
+  SH_TRY(o.ws(sh_ctx::WS_MISC, nq + nr, &oq));
+  orr = oq + nq;
+  SH_TRY(pa_divmod(o, x, n_a, y, n_b, oq, orr));
+  if (nq) SH_TRY(o.download(oq, q, nq));
+  if (nr) SH_TRY(o.download(orr, r, nr));
+  return SH_OK;
+}
+
+int sh_dev_mod_zpoly(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const void* d_xs, uint64_t n,
+                     void* d_out) {
+  static const char who[] = "sh_dev_mod_zpoly";
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(point_sizes(c, who, n));
+  if (!d_out || (n && !d_xs)) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (any_overlap(d_out, 32 * (n + 1), d_xs, 32 * n)) return fail(c, who, "the output overlaps the input", SH_ERR_INVALID);
+  ModOps o;
+  SH_TRY(o.init(c, who, modulus, root, root_log));
+  SH_TRY(o.fits(who, mp_max_transform(MP_OP_ZPOLY, n, 0)));
+  SH_TRY(enter(c));
+  return pa_zpoly(o, static_cast<const fpm*>(d_xs), n, static_cast<fpm*>(d_out));
+}
+
+int sh_mod_zpoly(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const uint8_t* xs, uint64_t n,
+                 uint8_t* out) {
+  static const char who[] = "sh_mod_zpoly";
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(point_sizes(c, who, n));
+  if (!out || (n && !xs)) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  ModOps o;
+  SH_TRY(o.init(c, who, modulus, root, root_log));
+  SH_TRY(o.fits(who, mp_max_transform(MP_OP_ZPOLY, n, 0)));
+  SH_TRY(enter(c));
+  fpm *x = nullptr, *d_out;
+  if (n) SH_TRY(o.upload(xs, n, sh_ctx::WS_X, &x));
+  SH_TRY(o.ws(sh_ctx::WS_MISC, n + 1, &d_out));
+  SH_TRY(pa_zpoly(o, static_cast<const fpm*>(x), n, d_out));
+  return o.download(d_out, out, n + 1);
+}
+
+int sh_dev_mod_lagrange_interp(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const void* d_xs,
+                               const void* d_ys, uint64_t n, void* d_out) {
+  static const char who[] = "sh_dev_mod_lagrange_interp";
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(point_sizes(c, who, n));
+  if (n && (!d_xs || !d_ys || !d_out)) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (any_overlap(d_out, 32 * n, d_xs, 32 * n) || any_overlap(d_out, 32 * n, d_ys, 32 * n))
+    return fail(c, who, "the output overlaps an input", SH_ERR_INVALID);
+  ModOps o;
+  SH_TRY(o.init(c, who, modulus, root, root_log));
+  SH_TRY(o.fits(who, mp_max_transform(MP_OP_LAGRANGE, n, 0)));
+  if (n == 0) return SH_OK;
+  SH_TRY(enter(c));
+  return pa_lagrange(o, static_cast<const fpm*>(d_xs), static_cast<const fpm*>(d_ys), n, static_cast<fpm*>(d_out));
+}
+
+int sh_mod_lagrange_interp(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const uint8_t* xs,
+                           const uint8_t* ys, uint64_t n, uint8_t* out) {
+  static const char who[] = "sh_mod_lagrange_interp";
+  if (!c) return SH_ERR_INVALID;
+  SH_TRY(point_sizes(c, who, n));
+  if (n && (!xs || !ys || !out)) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  ModOps o;
+  SH_TRY(o.init(c, who, modulus, root, root_log));
+  SH_TRY(o.fits(who, mp_max_transform(MP_OP_LAGRANGE, n, 0)));
+  if (n == 0) return SH_OK;
+  SH_TRY(enter(c));
+  fpm *x, *y, *d_out;
+  SH_TRY(o.upload(xs, n, sh_ctx::WS_X, &x));
+  SH_TRY(o.upload(ys, n, sh_ctx::WS_Y, &y));
+  SH_TRY(o.ws(sh_ctx::WS_MISC, n, &d_out));
+  SH_TRY(pa_lagrange(o, x, y, n, d_out));
+  return o.download(d_out, out, n);
+}
+}  // extern "C"

@@ -292,3 +292,23 @@ hipError_t shk_m6s_scalars(const uint32_t* d_mnodes, uint64_t tree_words, uint32
                            const f64_mod& M, hipStream_t st);
 hipError_t shk_m6s_lincomb(const M6sArgs& a, const uint64_t* d_scal, uint64_t* d_l, const f64_mod& M, hipStream_t st);
 hipError_t shk_m6s_gather(const M6sArgs& a, const M6sGather& ga, hipStream_t st);
+
+// ---- modpoly.hip: polynomial arithmetic and batch inversion over any prime modulus below 2^256 (modpoly_items.cuh; every array holds
+// PLAIN values, the modulus block is an argument of every launch) ------------------------------------------------------------------------
+hipError_t shk_mp_copy(const PaCopy& c, const fpm* src, fpm* dst, const fpm_mod& M, hipStream_t st);
+// 32-byte big-endian wire values <-> limbs: a byte swap, its own inverse, nothing is reduced; src may equal dst
+hipError_t shk_mp_swap(const void* src, void* dst, uint64_t n, hipStream_t st);
+hipError_t shk_mp_tree(const fpm* hz, fpm* oz, const fpm* hn, fpm* on, uint32_t log2d, uint64_t nodes, const fpm_mod& M, hipStream_t st);
+hipError_t shk_mp_mid(const fpm* hd, fpm* hr, uint32_t log2d, uint64_t children, const fpm_mod& M, hipStream_t st);
+hipError_t shk_mp_newton(const fpm* F, fpm* G, uint64_t n, const fpm_mod& M, hipStream_t st);
+hipError_t shk_mp_inv1(const fpm* src, fpm* dst, const fpm_mod& M, hipStream_t st);
+hipError_t shk_mp_deriv_rev(const fpm* top, fpm* out, uint64_t N, uint64_t n, const fpm_mod& M, hipStream_t st);
+hipError_t shk_mp_weights(const fpm* ys, const fpm* inv, fpm* out, uint64_t n, uint64_t N, const fpm_mod& M, hipStream_t st);
+hipError_t shk_mp_sub(const fpm* a, const fpm* b, fpm* out, uint64_t n, const fpm_mod& M, hipStream_t st);
+// scratch: elements of the levels above the items (0 when they fit one tile)
+uint64_t shk_mp_multi_inv_scratch(uint64_t n);
+uint64_t shk_mp_multi_interp_4_scratch(uint64_t rows);
+// out[i] = in[i]^-1, 0 for in[i] == 0 mod p; in may equal out; n >= 1
+hipError_t shk_mp_multi_inv(const fpm* in, fpm* out, uint64_t n, fpm* scratch, const fpm_mod& M, hipStream_t st);
+// xs, ys, coeffs: [rows][4]; coeffs may equal xs or ys; rows >= 1
+hipError_t shk_mp_multi_interp_4(const fpm* xs, const fpm* ys, fpm* coeffs, uint64_t rows, fpm* scratch, const fpm_mod& M, hipStream_t st);

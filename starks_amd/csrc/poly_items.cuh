@@ -105,7 +105,7 @@ FP_HD fp pa_weight(const fp& y, const fp& inv) {
 //                                                  (zero beyond; n_in = 0: n), the inverse scaled by 1/n; src may equal dst when n_in = 0
 //      int copy(PaCopy, src, dst), pointwise(a, b, out, n), tree(hz, oz, hn, on, log2d, nodes), mid(hd, hr, log2d, children),
 //      newton(F, G, n), inv1(src, dst), deriv_rev(top, out, N, n), multi_inv(in, out, n), weights(ys, inv, out, n, N), sub(a, b, out, n)
-//      int buf(slot, elems, fp**)                      scratch that stays valid for the call (one request per slot per call)
+//      int buf(slot, elems, E**)                      scratch that stays valid for the call (one request per slot per call)
 // Every call returns 0 or an error code, which the drivers pass on.
 #define PA_TRY(expr)           \
   do {                         \
@@ -125,15 +125,22 @@ inline uint32_t pa_log2(uint64_t n) {
   while ((1ull << k) < n) ++k;
   return k;
 }
-template <class Ops>
-int pa_cp(Ops& o, const fp* src, fp* dst, uint64_t rows, uint64_t len, uint64_t ss, uint64_t ds, uint64_t src_len, int64_t off, int dir,
+// The drivers are templates over the element type E as well, deduced from their pointer arguments: fp here (api_poly.hip), fpm for the
+// entries over a run-time modulus (api_modpoly.hip, whose Ops carries the modulus).  A parameter written pa_id<E>::type* takes no part
+// in the deduction, so a call may pass nullptr there.
+template <class T>
+struct pa_id {
+  typedef T type;
+};
+template <class Ops, class E>
+int pa_cp(Ops& o, const typename pa_id<E>::type* src, E* dst, uint64_t rows, uint64_t len, uint64_t ss, uint64_t ds, uint64_t src_len, int64_t off, int dir,
           uint32_t flags) {
   return o.copy(PaCopy{rows, len, ss, ds, src_len, off, (int32_t)dir, flags}, src, dst);
 }
 
 // out[0, na + nb - 1) = a b, canonical; na, nb >= 1; out must not alias a or b; t1, t2: pa_pow2_at_least(na + nb - 1) elements each
-template <class Ops>
-int pa_mul(Ops& o, const fp* a, uint64_t na, const fp* b, uint64_t nb, fp* out, fp* t1, fp* t2) {
+template <class Ops, class E>
+int pa_mul(Ops& o, const E* a, uint64_t na, const E* b, uint64_t nb, E* out, E* t1, E* t2) {
   const uint64_t nc = na + nb - 1, S = pa_pow2_at_least(nc);
   PA_TRY(o.ntt(a, t1, 1, S, na, false));
   PA_TRY(o.ntt(b, t2, 1, S, nb, false));
@@ -145,8 +152,8 @@ int pa_mul(Ops& o, const fp* a, uint64_t na, const fp* b, uint64_t nb, fp* out, 
 // elements t1 and t2 of pa_inverse need for L coefficients
 inline uint64_t pa_inverse_scratch(uint64_t L) { return 2 * pa_pow2_at_least(L); }
 // g[0, L) = f^-1 mod X^L by Newton's iteration (precision 1, 2, 4, ..., L); f is given by its first nf >= 1 coefficients, f[0] != 0
-template <class Ops>
-int pa_inverse(Ops& o, const fp* f, uint64_t nf, uint64_t L, fp* g, fp* t1, fp* t2) {
+template <class Ops, class E>
+int pa_inverse(Ops& o, const E* f, uint64_t nf, uint64_t L, E* g, E* t1, E* t2) {
   PA_TRY(o.inv1(f, g));
   for (uint64_t m = 1; m < L; m *= 2) {
     const uint64_t m2 = 2 * m < L ? 2 * m : L, S = pa_pow2_at_least(2 * m + m2 - 2);  // deg g^2 f < 2m + m2 - 2: no wrap-around
@@ -160,19 +167,19 @@ int pa_inverse(Ops& o, const fp* f, uint64_t nf, uint64_t L, fp* g, fp* t1, fp* 
 }
 
 // q[0, na - nb + 1) and r[0, nb - 1) with a = q b + r (na >= nb); or, for na < nb, q empty and r[0, na) = a.  b[nb - 1] != 0 mod p.
-template <class Ops>
-int pa_divmod(Ops& o, const fp* a, uint64_t na, const fp* b, uint64_t nb, fp* q, fp* r) {
+template <class Ops, class E>
+int pa_divmod(Ops& o, const E* a, uint64_t na, const E* b, uint64_t nb, E* q, E* r) {
   if (na < nb) return pa_cp(o, a, r, 1, na, 0, 0, na, 0, 1, PA_CANON);
   const uint64_t L = na - nb + 1, lb = nb < L ? nb : L;
   uint64_t S = pa_inverse_scratch(L);
   if (pa_pow2_at_least(2 * L - 1) > S) S = pa_pow2_at_least(2 * L - 1);
   if (pa_pow2_at_least(na) > S) S = pa_pow2_at_least(na);
-  fp *t1, *t2, *w, *qb;
+  E *t1, *t2, *w, *qb;
   PA_TRY(o.buf(PA_BUF_1, S, &t1));
   PA_TRY(o.buf(PA_BUF_2, S, &t2));
   PA_TRY(o.buf(PA_BUF_3, 5 * L, &w));
   PA_TRY(o.buf(PA_BUF_4, na, &qb));
-  fp *ra = w, *rb = w + L, *g = w + 2 * L, *qr = w + 3 * L;  // qr: 2L - 1
+  E *ra = w, *rb = w + L, *g = w + 2 * L, *qr = w + 3 * L;  // qr: 2L - 1
   PA_TRY(pa_cp(o, a, ra, 1, L, 0, 0, na, (int64_t)na - 1, -1, 0));   // rev(a) mod X^L
   PA_TRY(pa_cp(o, b, rb, 1, lb, 0, 0, nb, (int64_t)nb - 1, -1, 0));  // rev(b) mod X^L
   PA_TRY(pa_inverse(o, rb, lb, L, g, t1, t2));
@@ -184,17 +191,18 @@ int pa_divmod(Ops& o, const fp* a, uint64_t na, const fp* b, uint64_t nb, fp* q,
 }
 
 // level j of a product tree over N points: [N >> j] monic nodes of degree 2^j, their 2^j lower coefficients each
-inline fp* pa_level(fp* tree, uint64_t N, uint32_t j, bool keep) { return tree + (keep ? j : (j & 1)) * N; }
+template <class E>
+inline E* pa_level(E* tree, uint64_t N, uint32_t j, bool keep) { return tree + (keep ? j : (j & 1)) * N; }
 
 // the product tree of x_0 .. x_{n-1} padded with zeros to N points; keep: every level in tree[(lg + 1) N], else two alternating
 // levels in tree[2N] (the top is pa_level(tree, N, lg, keep)); hat: 2N elements
-template <class Ops>
-int pa_tree_up(Ops& o, const fp* xs, uint64_t n, uint64_t N, fp* tree, bool keep, fp* hat) {
+template <class Ops, class E>
+int pa_tree_up(Ops& o, const E* xs, uint64_t n, uint64_t N, E* tree, bool keep, E* hat) {
   const uint32_t lg = pa_log2(N);
   PA_TRY(pa_cp(o, xs, pa_level(tree, N, 0, keep), 1, N, 0, 0, n, 0, 1, PA_NEG));  // X - x_i, X beyond n
   for (uint32_t j = 0; j < lg; ++j) {
     const uint64_t d = 1ull << j, nodes = N >> j;
-    fp *lo = pa_level(tree, N, j, keep), *up = pa_level(tree, N, j + 1, keep);
+    E *lo = pa_level(tree, N, j, keep), *up = pa_level(tree, N, j + 1, keep);
     PA_TRY(o.ntt(lo, hat, nodes, 2 * d, d, false));
     PA_TRY(o.tree(hat, up, nullptr, nullptr, j + 1, nodes));
     PA_TRY(o.ntt(up, up, nodes / 2, 2 * d, 0, true));
@@ -203,11 +211,11 @@ int pa_tree_up(Ops& o, const fp* xs, uint64_t n, uint64_t N, fp* tree, bool keep
 }
 
 // out[0, n + 1) = prod (X - x_i), leading 1
-template <class Ops>
-int pa_zpoly(Ops& o, const fp* xs, uint64_t n, fp* out) {
+template <class Ops, class E>
+int pa_zpoly(Ops& o, const E* xs, uint64_t n, E* out) {
   if (n == 0) return pa_cp(o, nullptr, out, 1, 1, 0, 0, 0, 0, 1, PA_ONE_AT_END);
   const uint64_t N = pa_pow2_at_least(n);
-  fp *tree, *hat;
+  E *tree, *hat;
   PA_TRY(o.buf(PA_BUF_TREE, 2 * N, &tree));
   PA_TRY(o.buf(PA_BUF_3, 2 * N, &hat));
   PA_TRY(pa_tree_up(o, xs, n, N, tree, false, hat));
@@ -220,9 +228,9 @@ int pa_zpoly(Ops& o, const fp* xs, uint64_t n, fp* out) {
 // polynomials at x_0 .. x_{N-1}.  Every level is one batched forward transform of the parents, one of the children's rev(Z_c), the
 // middle-product launch and one batched inverse transform.  Scratch: t1 rows N, t2 2N, hat 2 rows N elements; for rows > 1 also zt
 // (2N), from which the children's transforms are copied to every row (for one row they are made in hat directly).
-template <class Ops>
-int pa_descend(Ops& o, fp* tree, uint64_t N, uint64_t rows, fp* d0, fp* d1, fp* t1, fp* t2, fp* hat, fp* zt, fp** leaves) {
-  fp *dcur = d0, *dnext = d1;
+template <class Ops, class E>
+int pa_descend(Ops& o, E* tree, uint64_t N, uint64_t rows, E* d0, E* d1, E* t1, E* t2, E* hat, typename pa_id<E>::type* zt, E** leaves) {
+  E *dcur = d0, *dnext = d1;
   for (int j = (int)pa_log2(N) - 1; j >= 0; --j) {
     const uint64_t d = 1ull << j, children = N >> j;
     PA_TRY(o.ntt(dcur, t1, rows * children / 2, 2 * d, 0, false));
@@ -237,7 +245,7 @@ int pa_descend(Ops& o, fp* tree, uint64_t N, uint64_t rows, fp* d0, fp* d1, fp* 
     PA_TRY(o.mid(t1, hat, (uint32_t)j + 1, rows * children));
     PA_TRY(o.ntt(hat, hat, rows * children, 2 * d, 0, true));
     PA_TRY(pa_cp(o, hat, dnext, rows * children, d, 2 * d, d, 2 * d, (int64_t)d, 1, 0));  // the middle: coefficients [d, 2d)
-    fp* t = dcur;
+    E* t = dcur;
     dcur = dnext;
     dnext = t;
   }
@@ -246,38 +254,38 @@ int pa_descend(Ops& o, fp* tree, uint64_t N, uint64_t rows, fp* d0, fp* d1, fp* 
 }
 
 // out[0, n) = sum_i y_i w_i prod_{j != i} (X - x_j), w_i = 1 / Z'(x_i), or 1 where Z'(x_i) = 0 (poly_utils.py:337-369); n >= 1
-template <class Ops>
-int pa_lagrange(Ops& o, const fp* xs, const fp* ys, uint64_t n, fp* out) {
+template <class Ops, class E>
+int pa_lagrange(Ops& o, const E* xs, const E* ys, uint64_t n, E* out) {
   const uint64_t N = pa_pow2_at_least(n);
   const uint32_t lg = pa_log2(N);
-  fp *tree, *hat, *t1, *t2, *r;
+  E *tree, *hat, *t1, *t2, *r;
   PA_TRY(o.buf(PA_BUF_TREE, (lg + 1) * N, &tree));
   PA_TRY(o.buf(PA_BUF_3, 2 * N, &hat));
   PA_TRY(o.buf(PA_BUF_1, 2 * N, &t1));
   PA_TRY(o.buf(PA_BUF_2, 2 * N, &t2));
   PA_TRY(o.buf(PA_BUF_5, 4 * N, &r));
-  fp* R[4] = {r, r + N, r + 2 * N, r + 3 * N};
+  E* R[4] = {r, r + N, r + 2 * N, r + 3 * N};
   PA_TRY(pa_tree_up(o, xs, n, N, tree, true, hat));
-  const fp* top = pa_level(tree, N, lg, true);
+  const E* top = pa_level(tree, N, lg, true);
   // the root of the scaled remainder tree: D = rev_{N-1}(Z') rev(Z)^-1 mod y^N; rev(Z)[k] = Z[N - k] (1 at k = 0)
   PA_TRY(pa_cp(o, top, R[2], 1, N, 0, 0, N, (int64_t)N, -1, PA_ONE_AT_END));
   PA_TRY(pa_inverse(o, R[2], N, N, R[0], t1, t2));
   PA_TRY(o.deriv_rev(top, R[1], N, n));
   PA_TRY(pa_mul(o, R[1], N, R[0], N, hat, t1, t2));  // 2N - 1 coefficients, the low N are D
   PA_TRY(pa_cp(o, hat, R[2], 1, N, 0, 0, N, 0, 1, 0));
-  fp* dcur = nullptr;
+  E* dcur = nullptr;
   PA_TRY(pa_descend(o, tree, N, 1, R[2], R[3], t1, t2, hat, nullptr, &dcur));
   // dcur[i] = Z'(x_i) = prod_{j != i} (x_i - x_j); the weights y_i / Z'(x_i) are the leaves of the numerator tree
   PA_TRY(o.multi_inv(dcur, t1, n));
   PA_TRY(o.weights(ys, t1, R[0], n, N));
-  fp *ncur = R[0], *nnext = R[1];
+  E *ncur = R[0], *nnext = R[1];
   for (uint32_t j = 0; j < lg; ++j) {
     const uint64_t d = 1ull << j, nodes = N >> j;
     PA_TRY(o.ntt(pa_level(tree, N, j, true), hat, nodes, 2 * d, d, false));
     PA_TRY(o.ntt(ncur, t1, nodes, 2 * d, d, false));
     PA_TRY(o.tree(hat, nullptr, t1, nnext, j + 1, nodes));
     PA_TRY(o.ntt(nnext, nnext, nodes / 2, 2 * d, 0, true));
-    fp* t = ncur;
+    E* t = ncur;
     ncur = nnext;
     nnext = t;
   }

@@ -8,10 +8,14 @@
     multi_eval(field, poly, xs) -> sequence          (poly(x) at every point: direct Horner lanes or a remainder tree)
     multi_inv_wire(data) -> bytes, multi_interp_4_wire(xs, ys, rows) -> bytes,
     zpoly_wire(xs) -> bytes, lagrange_interp_wire(xs, ys) -> bytes   (wire form in and out, for large inputs)
+    mod_multi_inv_wire(p, data), mod_multi_interp_4_wire(p, xs, ys, rows), mod_zpoly_wire(p, xs), mod_lagrange_interp_wire(p, xs, ys)
+                                                       (the same over any prime p < 2^256: sh_mod_*, always on the device)
 
 For the MiMC prime they always run on the GPU through libstarkhip.so (sh_multi_inv, sh_multi_interp_4) and raise when the library
-or the device is missing: there is no CPU fallback for them.  Another modulus (the reference's own tests use Z/7) is outside the hot
-path: there the reference's algorithm runs on the host on the field's own elements, as fft._host_dft does for transforms.
+or the device is missing: there is no CPU fallback for them.  Another PRIME field goes to the device's generic entries (sh_mod_*)
+when the process already holds a context, the call's largest transform fits the field's 2-adicity and the size is at or above the
+operation's measured threshold (MOD_DEVICE_MIN, _lib.mod_poly_routable).  Everything else (the reference's own tests use Z/7) is
+outside the hot path: there the reference's algorithm runs on the host on the field's own elements, as fft._host_dft does.
 
 The reference's multi_inv tests the truthiness of each value (poly_utils.py:317): a zero Python int comes back as 0, a zero FIELD
 ELEMENT -- always truthy -- as 1.  The device computes 0 for every zero; `multi_inv` puts the 1 back where the input was an element
@@ -28,6 +32,82 @@ from .wireseq import WireList
 
 def _on_device(field):
     return int(getattr(field, "p", 0)) == MIMC_P
+
+
+# Another prime field goes to the device (sh_mod_*, include/starkhip.h) from this many values / rows / points on, when
+# _lib.mod_poly_routable holds; None: routing is off for the operation.  Each is the smallest power of two from which the device call
+# won end to end at every larger measured size (tools/mod_poly_time.py over BN254 against the host loop on the same inputs in the same
+# run, profiles/r21_mod_poly.json, "routing": multi_inv 0.66 ms against 1.07 ms at 512 and 0.66 against 0.56 ms at 256; multi_interp_4
+# 0.75 against 0.79 ms at 16 rows; zpoly 0.63 against 1.38 ms at 64 and 0.36 against 0.35 ms at 32; lagrange_interp 3.0 against 9.1 ms
+# at 16 and 2.1 against 1.7 ms at 8).
+MOD_DEVICE_MIN = {"multi_inv": 512, "multi_interp_4": 16, "zpoly": 64, "lagrange_interp": 16}
+
+
+def _mod_on_device(field, what, size, op=None):
+    least = MOD_DEVICE_MIN[what]
+    p = getattr(field, "p", None)
+    if least is None or p is None or size < least:
+        return False
+    return _lib.mod_poly_routable(p, op, size)
+
+
+def _check_wire(*bufs):
+    out = []
+    for b in bufs:
+        b = bytes(b) if not isinstance(b, bytes) else b
+        if len(b) % 32:
+            raise ValueError("wire form is a multiple of 32 bytes")
+        out.append(b)
+    return out
+
+
+def mod_multi_inv_wire(modulus, data):
+    """multi_inv_wire over any prime modulus below 2^256 (sh_mod_multi_inv): n 32-byte big-endian values (any 256-bit value) -> their
+    inverses mod p, canonical, 0 for a value == 0 mod p.  Always on the device."""
+    data, = _check_wire(data)
+    n = len(data) // 32
+    if n == 0:
+        return b""
+    out = ctypes.create_string_buffer(32 * n)
+    _lib.check(_lib.lib().sh_mod_multi_inv(_lib.ctx(), int(modulus).to_bytes(32, "big"), data, n, out), "sh_mod_multi_inv")
+    return out.raw
+
+
+def mod_multi_interp_4_wire(modulus, xs, ys, rows):
+    """multi_interp_4_wire over any prime modulus below 2^256 (sh_mod_multi_interp_4).  Always on the device."""
+    xs, ys = _check_wire(xs, ys)
+    if len(xs) != 128 * rows or len(ys) != 128 * rows:
+        raise ValueError("xs and ys must hold 4 * rows 32-byte values")
+    if rows == 0:
+        return b""
+    out = ctypes.create_string_buffer(128 * rows)
+    _lib.check(_lib.lib().sh_mod_multi_interp_4(_lib.ctx(), int(modulus).to_bytes(32, "big"), xs, ys, rows, out), "sh_mod_multi_interp_4")
+    return out.raw
+
+
+def mod_zpoly_wire(modulus, xs, root=None):
+    """zpoly_wire over any prime modulus below 2^256 (sh_mod_zpoly); root = (root of unity, log2 of its order), default
+    _lib.two_adic_root(modulus).  Always on the device."""
+    xs, = _check_wire(xs)
+    n = len(xs) // 32
+    m, w, k = _lib.mod_poly_args(modulus, root)
+    out = ctypes.create_string_buffer(32 * (n + 1))
+    _lib.check(_lib.lib().sh_mod_zpoly(_lib.ctx(), m, w, k, xs, n, out), "sh_mod_zpoly")
+    return out.raw
+
+
+def mod_lagrange_interp_wire(modulus, xs, ys, root=None):
+    """lagrange_interp_wire over any prime modulus below 2^256 (sh_mod_lagrange_interp), repeated x's included.  Always on the device."""
+    xs, ys = _check_wire(xs, ys)
+    if len(ys) != len(xs):
+        raise ValueError("xs and ys must hold the same number of 32-byte values")
+    n = len(xs) // 32
+    if n == 0:
+        return b""
+    m, w, k = _lib.mod_poly_args(modulus, root)
+    out = ctypes.create_string_buffer(32 * n)
+    _lib.check(_lib.lib().sh_mod_lagrange_interp(_lib.ctx(), m, w, k, xs, ys, n, out), "sh_mod_lagrange_interp")
+    return out.raw
 
 
 def multi_inv_wire(data):
@@ -65,12 +145,15 @@ def _zero_rows(raw):
 
 def multi_inv(field, values):
     """starks/poly_utils.py:301-320: the inverse of every value, one field inversion in all."""
-    if not _on_device(field):
-        return _host_multi_inv(field, list(values))
+    mimc = _on_device(field)
+    if not mimc:
+        values = values if isinstance(values, (list, tuple, WireList)) else list(values)
+        if not _mod_on_device(field, "multi_inv", len(values)):
+            return _host_multi_inv(field, list(values))
     elements = isinstance(values, WireList)
     if not elements and not isinstance(values, (list, tuple)):
         values = list(values)
-    out = multi_inv_wire(_lib.to_wire(values))
+    out = multi_inv_wire(_lib.to_wire(values)) if mimc else mod_multi_inv_wire(field.p, _lib.to_wire(values, int(field.p)))
     zeros = _zero_rows(out)  # an inverse is 0 exactly where the value is 0 mod p
     if zeros:
         buf = bytearray(out)
@@ -87,10 +170,14 @@ def multi_interp_4(field, xsets, ysets):
     xsets, ysets = list(xsets), list(ysets)
     if len(xsets) != len(ysets) or any(len(r) != 4 for r in xsets) or any(len(r) != 4 for r in ysets):
         raise ValueError("multi_interp_4 takes rows of four x and four y values")
-    if not _on_device(field):
-        return _host_multi_interp_4(field, xsets, ysets)
     rows = len(xsets)
-    raw = multi_interp_4_wire(b"".join(_lib.to_wire(list(r)) for r in xsets), b"".join(_lib.to_wire(list(r)) for r in ysets), rows)
+    if not _on_device(field):
+        if not _mod_on_device(field, "multi_interp_4", rows):
+            return _host_multi_interp_4(field, xsets, ysets)
+        p = int(field.p)
+        raw = mod_multi_interp_4_wire(p, b"".join(_lib.to_wire(list(r), p) for r in xsets), b"".join(_lib.to_wire(list(r), p) for r in ysets), rows)
+    else:
+        raw = multi_interp_4_wire(b"".join(_lib.to_wire(list(r)) for r in xsets), b"".join(_lib.to_wire(list(r)) for r in ysets), rows)
     coeffs = WireList(raw, field)
     polys_over = polynomials_over(field)
     return [polys_over(coeffs[4 * r:4 * r + 4]) for r in range(rows)]
@@ -126,7 +213,10 @@ def zpoly(field, roots):
     """starks/poly_utils.py:322-335: the monic polynomial whose roots are `roots` (the reference's debug print is not kept)."""
     polys_over = polynomials_over(field)
     if not _on_device(field):
-        return polys_over(_host_zpoly(field, list(roots)))
+        roots = list(roots)
+        if _mod_on_device(field, "zpoly", len(roots), _lib.MOD_POLY_ZPOLY):
+            return polys_over(WireList(mod_zpoly_wire(field.p, _lib.to_wire(roots, int(field.p))), field))
+        return polys_over(_host_zpoly(field, roots))
     return polys_over(WireList(zpoly_wire(_lib.to_wire(roots)), field))
 
 
@@ -137,6 +227,9 @@ def lagrange_interp(field, xs, ys):
     assert len(xs) == len(ys)  # the reference: assert len(root) == len(ys) + 1
     polys_over = polynomials_over(field)
     if not _on_device(field):
+        if _mod_on_device(field, "lagrange_interp", len(xs), _lib.MOD_POLY_LAGRANGE):
+            p = int(field.p)
+            return polys_over(WireList(mod_lagrange_interp_wire(p, _lib.to_wire(xs, p), _lib.to_wire(ys, p)), field))
         return _host_lagrange_interp(field, xs, ys)
     return polys_over(WireList(lagrange_interp_wire(_lib.to_wire(xs), _lib.to_wire(ys)), field))
 

@@ -5,8 +5,11 @@ its `typecheck` does (numbertype.py:31-54).
 Over the MiMC field every product and division runs on the GPU at every size (sh_poly_mul, sh_poly_divmod: NTT products and a
 Newton inverse, O(n log n)); the result is backed by the device's bytes (a WireList, trailing zeros stripped on the bytes).  Calling
 such a device-backed polynomial at an int or field element runs sh_poly_eval from EVAL_DEVICE_MIN_COEFS coefficients on, when the
-process already holds a device context; every other call is the reference's loop.  Any
-other ring (the reference's own tests use Z/5, Z/7, Z/11 and Fraction) runs the reference's schoolbook algorithms on the host.
+process already holds a device context; every other call is the reference's loop.  Over another PRIME field products and
+divisions go to the device's generic entries (sh_mod_poly_mul, sh_mod_poly_divmod; mod_mul_wire and mod_divmod_wire always do) when
+the process already holds a context, the field's 2-adicity admits the call's transforms and the operands reach the measured threshold
+(MOD_DEVICE_MIN).  Any other ring or size (the reference's own tests use Z/5, Z/7, Z/11 and Fraction) runs the reference's schoolbook
+algorithms on the host.
 Errors are the reference's: `/` and `%` by the zero polynomial raise ZeroDivisionError, `divmod` by it raises IndexError (the
 reference reads the divisor's leading coefficient, polynomial.py:131)."""
 import ctypes
@@ -114,6 +117,13 @@ def polynomials_over(ring):
                 return Polynomial([])
             if _on_device(ring):
                 return Polynomial(WireList(mul_wire(_wire(self), _wire(other)), ring))
+            if _mod_on_device(ring, "mul", 0, len(self), len(other)):
+                return Polynomial(WireList(mod_mul_wire(ring.p, _wire(self, ring.p), _wire(other, ring.p)), ring))
+            return self._schoolbook(other)
+
+        def _schoolbook(self, other):
+            """the reference's product loop (polynomial.py:116-125), never routed: the host long division below multiplies by
+            monomials with it"""
             out = [ring(0) for _ in range(len(self) + len(other) - 1)]
             for i, a in enumerate(self.coefficients):
                 for j, b in enumerate(other.coefficients):
@@ -128,12 +138,15 @@ def polynomials_over(ring):
             if _on_device(ring):
                 q, r = divmod_wire(_wire(self), _wire(divisor))
                 return Polynomial(WireList(q, ring)), Polynomial(WireList(r, ring))
+            if _mod_on_device(ring, "divmod", 1, len(self), len(divisor)):
+                q, r = mod_divmod_wire(ring.p, _wire(self, ring.p), _wire(divisor, ring.p))
+                return Polynomial(WireList(q, ring)), Polynomial(WireList(r, ring))
             quotient, remainder = Polynomial([]), self
             deg = divisor.degree()
             while remainder.degree() >= deg:
                 mono = Polynomial([ring(0)] * (remainder.degree() - deg) + [remainder.leading_coefficient() / lc])
                 quotient = quotient + mono
-                remainder = remainder - mono * divisor
+                remainder = remainder - mono._schoolbook(divisor)
             return quotient, remainder
 
         def __rdivmod__(self, other):
@@ -214,9 +227,56 @@ def _on_device(ring):
     return int(getattr(ring, "p", 0)) == MIMC_P
 
 
-def _wire(poly):
+# Another prime field: products and divisions go to the device (sh_mod_poly_mul, sh_mod_poly_divmod) when _lib.mod_poly_routable holds
+# and the SHORTER side of the work -- min(n_a, n_b) of a product, min(n_a - n_b + 1, n_b) (quotient and divisor lengths) of a division --
+# has at least this many coefficients; None: routing is off for the operation.  The host loops cost n_a n_b and (n_a - n_b + 1) n_b
+# ring products, so the shorter side bounds them from below by the measured square shapes.  Each value is the smallest power of two
+# from which the device call won end to end at every larger measured size (tools/mod_poly_time.py over BN254 against the host loops
+# above on the same inputs in the same run, profiles/r21_mod_poly.json, "routing": n x n products 0.22 ms against 0.67 ms at 32 and
+# 0.24 against 0.19 ms at 16; 2n-by-n divisions 1.7 ms against 2.6 ms at n = 16 and 1.5 against 0.9 ms at 8).
+MOD_DEVICE_MIN = {"mul": 32, "divmod": 16}
+
+
+def _mod_on_device(ring, what, op, n_a, n_b):
+    least = MOD_DEVICE_MIN[what]
+    p = getattr(ring, "p", None)
+    if least is None or p is None or min(n_a - n_b + 1 if what == "divmod" else n_a, n_b) < least:
+        return False
+    return _lib_mod().mod_poly_routable(p, op, n_a, n_b)
+
+
+def _wire(poly, modulus=None):
     from . import _lib
-    return _lib.to_wire(poly.coefficients)
+    return _lib.to_wire(poly.coefficients) if modulus is None else _lib.to_wire(poly.coefficients, int(modulus))
+
+
+def mod_mul_wire(modulus, a, b, root=None):
+    """mul_wire over any prime modulus below 2^256 (sh_mod_poly_mul); root = (root of unity, log2 of its order), default
+    _lib.two_adic_root(modulus).  Always on the device."""
+    from . import _lib
+    a, b = _as_bytes(a), _as_bytes(b)
+    na, nb = len(a) // 32, len(b) // 32
+    if na == 0 or nb == 0:
+        return b""
+    m, w, k = _lib.mod_poly_args(modulus, root)
+    out = ctypes.create_string_buffer(32 * (na + nb - 1))
+    _lib.check(_lib.lib().sh_mod_poly_mul(_lib.ctx(), m, w, k, a, na, b, nb, out), "sh_mod_poly_mul")
+    return out.raw
+
+
+def mod_divmod_wire(modulus, a, b, root=None):
+    """divmod_wire over any prime modulus below 2^256 (sh_mod_poly_divmod).  Always on the device."""
+    from . import _lib
+    a, b = _as_bytes(a), _as_bytes(b)
+    na, nb = len(a) // 32, len(b) // 32
+    if nb == 0:
+        raise ZeroDivisionError
+    nq, nr = max(na - nb + 1, 0), min(na, nb - 1)
+    m, w, k = _lib.mod_poly_args(modulus, root)
+    q = ctypes.create_string_buffer(32 * max(nq, 1))
+    r = ctypes.create_string_buffer(32 * max(nr, 1))
+    _lib.check(_lib.lib().sh_mod_poly_divmod(_lib.ctx(), m, w, k, a, na, b, nb, q, r), "sh_mod_poly_divmod")
+    return q.raw[:32 * nq], r.raw[:32 * nr]
 
 
 def _as_bytes(data):
