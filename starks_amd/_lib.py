@@ -161,6 +161,8 @@ def lib():
         "sh_mod_zpoly": (i32, [c_p, u8p, u8p, u32, u8p, u64, c_p]),
         "sh_dev_mod_lagrange_interp": (i32, [c_p, u8p, u8p, u32, c_p, c_p, u64, c_p]),
         "sh_mod_lagrange_interp": (i32, [c_p, u8p, u8p, u32, u8p, u8p, u64, c_p]),
+        "sh_dev_mod_poly_eval": (i32, [c_p, u8p, u8p, u32, c_p, u64, u32, c_p, u64, c_p]),
+        "sh_mod_poly_eval": (i32, [c_p, u8p, u8p, u32, u8p, u64, u32, u8p, u64, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares
@@ -305,7 +307,7 @@ def order_of_root(root, modulus=MIMC_P):
 
 
 # ---- roots of unity and primality for the polynomial entries over a run-time modulus (sh_mod_poly_*) ----------------------------------
-MOD_POLY_MUL, MOD_POLY_DIVMOD, MOD_POLY_ZPOLY, MOD_POLY_LAGRANGE = 0, 1, 2, 3  # sh_mod_poly_max_transform's op
+MOD_POLY_MUL, MOD_POLY_DIVMOD, MOD_POLY_ZPOLY, MOD_POLY_LAGRANGE, MOD_POLY_EVAL = 0, 1, 2, 3, 4  # sh_mod_poly_max_transform's op
 MAX_ROOT_LOG = 26  # the generic transform's largest size
 _two_adic = {}
 _prime = {}
@@ -381,6 +383,6 @@ def mod_poly_routable(p, op, n_a, n_b=0):
     p = int(p)
     if p == MIMC_P or p < 3 or p % 2 == 0 or p >> 256 or not is_probable_prime(p):
         return False
-    if op is None:  # multi_inv, multi_interp_4: no transform
+    if op is None:  # multi_inv, multi_interp_4: no transform; evaluation: the direct path is always available
         return True
     return lib().sh_mod_poly_max_transform(op, n_a, n_b) <= 1 << two_adic_root(p)[1]

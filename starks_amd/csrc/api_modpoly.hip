@@ -1,7 +1,8 @@
 // api_modpoly.hip -- polynomial products, division, zpoly, lagrange_interp, batch inversion and four-point interpolation over any prime
-// modulus below 2^256 on the host side: the drivers of poly_items.cuh over the generic transform (api_modntt.hip: mod_table, mod_run)
-// and the kernels of modpoly.hip.  Every check runs here before the first launch; every error text opens with the entry's name.
+// modulus below 2^256, and evaluation at arbitrary points (sh_mod_poly_eval), on the host side: the drivers of poly_items.cuh over the generic transform (api_modntt.hip: mod_table, mod_run)
+// and the kernels of modpoly.hip and modeval.hip.  Every check runs here before the first launch; every error text opens with the entry's name.
 #include "ctx.hpp"
+#include "modeval_items.cuh"
 #include "modpoly_items.cuh"
 using namespace shk;
 
@@ -107,6 +108,21 @@ struct ModOps {
     return SH_OK;
   }
   int sub(const fpm* a, const fpm* b, fpm* out, uint64_t n) { HIP_TRY(c, shk_mp_sub(a, b, out, n, M, c->stream)); return SH_OK; }
+  int eval_pow_table(const fpm* xs, uint64_t m, uint32_t lgS, fpm* tbl) { HIP_TRY(c, shk_me_pow_table(xs, m, lgS, tbl, M, c->stream)); return SH_OK; }
+  int eval_direct(const PeDirect& s, const fpm* coefs, const fpm* tbl, fpm* dst) {
+    HIP_TRY(c, shk_me_direct(s, coefs, tbl, dst, M, c->stream));
+    return SH_OK;
+  }
+  int eval_sum(const PeDirect& s, const fpm* part, fpm* out) { HIP_TRY(c, shk_me_sum(s, part, out, M, c->stream)); return SH_OK; }
+  int eval_chunks(const fpm* coefs, uint64_t n, uint64_t batch, uint64_t N, uint64_t C, fpm* dst) {
+    HIP_TRY(c, shk_me_chunks(coefs, n, batch, N, C, dst, c->stream));
+    return SH_OK;
+  }
+  int bcast_mul(fpm* a, const fpm* b, uint64_t rows, uint64_t len) { HIP_TRY(c, shk_me_bcast_mul(a, b, rows, len, M, c->stream)); return SH_OK; }
+  int eval_combine(const fpm* leaves, const fpm* xs, uint64_t m, uint64_t N, uint64_t C, uint64_t batch, fpm* out) {
+    HIP_TRY(c, shk_me_combine(leaves, xs, m, N, C, batch, out, M, c->stream));
+    return SH_OK;
+  }
   int buf(int slot, uint64_t elems, fpm** out) { return ws(sh_ctx::WS_PA_TREE + slot, elems, out); }
   int ws(int slot, uint64_t elems, fpm** out) {
     void* p = nullptr;
@@ -143,6 +159,27 @@ int divmod_sizes(sh_ctx* c, const char* who, uint64_t n_a, uint64_t n_b) {
 }
 int point_sizes(sh_ctx* c, const char* who, uint64_t n) {
   if (n > MP_MAX_POINTS) return fail(c, who, "the points are limited to 2^20", SH_ERR_INVALID);
+  return SH_OK;
+}
+
+// sh_mod_poly_eval's limits and checks (sh_poly_eval's: api_poly.hip), the modulus and the root, then the path: STARKHIP_EVAL_PATH,
+// else the direct path when the tree's transform exceeds the root's order, else modeval_items.cuh's cost rule.  A forced tree that
+// does not fit is refused here, before any launch.
+constexpr uint64_t ME_MAX_COEFS = 1ull << 25, ME_MAX_TOTAL = 1ull << 26, ME_MAX_POINTS = 1ull << 20;
+int eval_check(sh_ctx* c, const char* who, ModOps* o, const uint8_t* modulus, const uint8_t* root, uint32_t root_log, const void* coefs,
+               uint64_t n, uint32_t batch, const void* xs, uint64_t m, const void* out, bool* direct) {
+  if (batch == 0) return fail(c, who, "batch is zero", SH_ERR_INVALID);
+  if ((n && !coefs) || (m && (!xs || !out))) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (n > ME_MAX_COEFS) return fail(c, who, "a polynomial is limited to 2^25 coefficients", SH_ERR_UNSUPPORTED);
+  if ((uint64_t)batch * n > ME_MAX_TOTAL) return fail(c, who, "the polynomials are limited to 2^26 coefficients in all", SH_ERR_UNSUPPORTED);
+  if (m > ME_MAX_POINTS) return fail(c, who, "the points are limited to 2^20", SH_ERR_UNSUPPORTED);
+  const uint64_t out_bytes = 32ull * batch * m;
+  if (any_overlap(out, out_bytes, coefs, 32ull * batch * n) || any_overlap(out, out_bytes, xs, 32 * m))
+    return fail(c, who, "the output overlaps an input", SH_ERR_INVALID);
+  SH_TRY(o->init(c, who, modulus, root, root_log));
+  const int forced = shk_knobs().eval_path;
+  *direct = forced ? forced == 1 : me_direct_preferred(n, m, batch, root_log);
+  if (!*direct) SH_TRY(o->fits(who, mp_max_transform(MP_OP_EVAL, n, m)));
   return SH_OK;
 }
 }  // namespace
@@ -370,5 +407,34 @@ int sh_mod_lagrange_interp(sh_ctx* c, const uint8_t modulus[32], const uint8_t r
   SH_TRY(o.ws(sh_ctx::WS_MISC, n, &d_out));
   SH_TRY(pa_lagrange(o, x, y, n, d_out));
   return o.download(d_out, out, n);
+}
+
+int sh_dev_mod_poly_eval(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const void* d_coefs, uint64_t n,
+                         uint32_t batch, const void* d_xs, uint64_t m, void* d_out) {
+  static const char who[] = "sh_dev_mod_poly_eval";
+  if (!c) return SH_ERR_INVALID;
+  ModOps o;
+  bool direct = true;
+  SH_TRY(eval_check(c, who, &o, modulus, root, root_log, d_coefs, n, batch, d_xs, m, d_out, &direct));
+  if (m == 0) return SH_OK;
+  SH_TRY(enter(c));
+  return pa_eval(o, static_cast<const fpm*>(d_coefs), n, batch, static_cast<const fpm*>(d_xs), m, static_cast<fpm*>(d_out), direct);
+}
+
+int sh_mod_poly_eval(sh_ctx* c, const uint8_t modulus[32], const uint8_t root[32], uint32_t root_log, const uint8_t* coefs, uint64_t n,
+                     uint32_t batch, const uint8_t* xs, uint64_t m, uint8_t* out) {
+  static const char who[] = "sh_mod_poly_eval";
+  if (!c) return SH_ERR_INVALID;
+  ModOps o;
+  bool direct = true;
+  SH_TRY(eval_check(c, who, &o, modulus, root, root_log, coefs, n, batch, xs, m, out, &direct));
+  if (m == 0) return SH_OK;
+  SH_TRY(enter(c));
+  fpm *x = nullptr, *d_xs, *d_out;
+  if (n) SH_TRY(o.upload(coefs, (uint64_t)batch * n, sh_ctx::WS_X, &x));
+  SH_TRY(o.upload(xs, m, sh_ctx::WS_Y, &d_xs));
+  SH_TRY(o.ws(sh_ctx::WS_MISC, (uint64_t)batch * m, &d_out));
+  SH_TRY(pa_eval(o, static_cast<const fpm*>(x), n, batch, static_cast<const fpm*>(d_xs), m, d_out, direct));
+  return o.download(d_out, out, (uint64_t)batch * m);
 }
 }  // extern "C"

@@ -312,3 +312,15 @@ uint64_t shk_mp_multi_interp_4_scratch(uint64_t rows);
 hipError_t shk_mp_multi_inv(const fpm* in, fpm* out, uint64_t n, fpm* scratch, const fpm_mod& M, hipStream_t st);
 // xs, ys, coeffs: [rows][4]; coeffs may equal xs or ys; rows >= 1
 hipError_t shk_mp_multi_interp_4(const fpm* xs, const fpm* ys, fpm* coeffs, uint64_t rows, fpm* scratch, const fpm_mod& M, hipStream_t st);
+
+// ---- modeval.hip: evaluation at arbitrary points over any prime modulus below 2^256 (modeval_items.cuh; poly_items.cuh: pa_eval_direct,
+// pa_eval_tree).  Plain values everywhere but tbl, which holds Montgomery forms ---------------------------------------------------------
+// tbl[b m + i] = x_i^(2^b) R, b <= lgS
+hipError_t shk_me_pow_table(const fpm* xs, uint64_t m, uint32_t lgS, fpm* tbl, const fpm_mod& M, hipStream_t st);
+// dst[b][w][i]: workgroup w's sum for point i of polynomial b, canonical; coefs [batch][n], any 256-bit values
+hipError_t shk_me_direct(const PeDirect& s, const fpm* coefs, const fpm* tbl, fpm* dst, const fpm_mod& M, hipStream_t st);
+hipError_t shk_me_sum(const PeDirect& s, const fpm* part, fpm* out, const fpm_mod& M, hipStream_t st);
+hipError_t shk_me_chunks(const fpm* coefs, uint64_t n, uint64_t batch, uint64_t N, uint64_t C, fpm* dst, hipStream_t st);
+hipError_t shk_me_bcast_mul(fpm* a, const fpm* b, uint64_t rows, uint64_t len, const fpm_mod& M, hipStream_t st);
+hipError_t shk_me_combine(const fpm* leaves, const fpm* xs, uint64_t m, uint64_t N, uint64_t C, uint64_t batch, fpm* out, const fpm_mod& M,
+                          hipStream_t st);

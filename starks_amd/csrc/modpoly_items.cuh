@@ -78,7 +78,7 @@ FPM_HD fpm mp_sub(const fpm& a, const fpm& b, const fpm_mod& M) { return fpm_sub
 
 // The largest transform a call runs: what the drivers of poly_items.cuh ask of Ops::ntt for these sizes (the host test compares it
 // with what its Ops saw).  0: the call runs no transform.
-enum : int { MP_OP_MUL = 0, MP_OP_DIVMOD = 1, MP_OP_ZPOLY = 2, MP_OP_LAGRANGE = 3 };
+enum : int { MP_OP_MUL = 0, MP_OP_DIVMOD = 1, MP_OP_ZPOLY = 2, MP_OP_LAGRANGE = 3, MP_OP_EVAL = 4 };
 inline uint64_t mp_max_transform(int op, uint64_t na, uint64_t nb) {
   auto mx = [](uint64_t a, uint64_t b) { return a > b ? a : b; };
   switch (op) {
@@ -96,6 +96,8 @@ inline uint64_t mp_max_transform(int op, uint64_t na, uint64_t nb) {
       return na ? pa_pow2_at_least(na) : 0;
     case MP_OP_LAGRANGE:
       return na ? 2 * pa_pow2_at_least(na) : 0;  // the root product of the remainder tree
+    case MP_OP_EVAL:
+      return na && nb ? 2 * pa_pow2_at_least(nb) : 0;  // na coefficients at nb points on the tree path (the direct path runs none)
   }
   return 0;
 }

@@ -308,7 +308,7 @@ FP_HD void pa_st(fp* p, const fp& v) {
 // are added across the workgroup and, when W > 1, across workgroups by a second launch: modular addition is exact, so neither the
 // grid shape nor the order changes a bit of the result.  About batch n m products; the coefficients are read once per point group.
 constexpr uint32_t PE_WG = 256;           // lanes per workgroup
-constexpr uint32_t PE_GROUP = 4;          // points per lane when m >= 4 (else 1)
+constexpr uint32_t PE_GROUP = 4;          // points per lane when m >= 4 (else 1) over fp; pe_group<E> names another element type's
 constexpr uint64_t PE_MIN_T = 64;         // W doubles only while every lane keeps at least this many coefficients
 constexpr uint64_t PE_TARGET_WGS = 2048;  // ... and the grid is below this many workgroups (8 per CU)
 struct PeDirect {
@@ -318,14 +318,20 @@ struct PeDirect {
   uint64_t groups;  // point groups, ceil(m / G)
   uint32_t lgS, G;
 };
-inline PeDirect pe_direct_shape(uint64_t n, uint64_t m, uint64_t batch) {
-  PeDirect s{n, m, batch, 1, 0, 0, 0, m >= PE_GROUP ? PE_GROUP : 1u};
+template <class E>
+struct pe_group {
+  static constexpr uint32_t value = PE_GROUP;
+};
+template <uint32_t GROUP>
+inline PeDirect pe_direct_shape_of(uint64_t n, uint64_t m, uint64_t batch) {
+  PeDirect s{n, m, batch, 1, 0, 0, 0, m >= GROUP ? GROUP : 1u};
   s.groups = (m + s.G - 1) / s.G;
   while (2 * s.W * PE_WG * PE_MIN_T <= n && s.W * s.groups * batch < PE_TARGET_WGS) s.W *= 2;
   s.lgS = pa_log2(s.W * PE_WG);
   s.T = (n + (s.W << 8) - 1) / (s.W << 8);
   return s;
 }
+inline PeDirect pe_direct_shape(uint64_t n, uint64_t m, uint64_t batch) { return pe_direct_shape_of<PE_GROUP>(n, m, batch); }
 
 // tbl[b m + i] = x_i^(2^b), b <= lgS (y = x^S is entry lgS)
 FP_HD void pe_pow_table_item(const fp* xs, uint64_t m, uint32_t lgS, fp* tbl, uint64_t i) {
@@ -391,32 +397,38 @@ FP_HD fp pe_combine_item(const fp* leaves, const fp* xs, uint64_t N, uint64_t C,
   return fp_canon(acc);
 }
 
-// Path choice: the direct path costs about batch n m products at 1.9e5 per us plus a 50 us floor; the tree about 150 us of launches
-// per level, its batched transforms (N lg^2 elements for the tree and the inverse, 3 R N lg for the R = batch C rows' root step and
-// descent, at 8e4 elements per us) and 0.8 us per row (the batched transforms of many short rows).  The constants are fitted to the
-// MI355X times of both forced paths over twelve shapes (profiles/r10_poly_eval.json, crossover_ms), which put the crossover near
-// n m = 2^29 for n = m / 4 .. 8 m: (2^15, 2^13) direct, (2^16, 2^13) tree.
+// Path choice: the direct path costs about batch n m products at products_per_us plus a floor; the tree us_per_level of launches per
+// level, its batched transforms (N lg^2 elements for the tree and the inverse, 3 R N lg for the R = batch C rows' root step and
+// descent, at elements_per_us) and us_per_row per row (the batched transforms of many short rows).  The constants are data, one set
+// per field.  The MiMC set is fitted to the MI355X times of both forced paths over twelve shapes (profiles/r10_poly_eval.json,
+// crossover_ms), which put the crossover near n m = 2^29 for n = m / 4 .. 8 m: (2^15, 2^13) direct, (2^16, 2^13) tree.
+struct PeCost {
+  double direct_products_per_us, direct_floor_us, tree_us_per_level, tree_elements_per_us, tree_us_per_row;
+};
 constexpr double PE_DIRECT_PRODUCTS_PER_US = 1.9e5;
 constexpr double PE_DIRECT_FLOOR_US = 50.0;
 constexpr double PE_TREE_US_PER_LEVEL = 150.0;
 constexpr double PE_TREE_ELEMENTS_PER_US = 8.0e4;
 constexpr double PE_TREE_US_PER_ROW = 0.8;
-inline bool pe_direct_preferred(uint64_t n, uint64_t m, uint64_t batch) {
+constexpr PeCost PE_COST_MIMC = {PE_DIRECT_PRODUCTS_PER_US, PE_DIRECT_FLOOR_US, PE_TREE_US_PER_LEVEL, PE_TREE_ELEMENTS_PER_US, PE_TREE_US_PER_ROW};
+inline bool pe_direct_preferred(const PeCost& k, uint64_t n, uint64_t m, uint64_t batch) {
   const uint64_t N = pa_pow2_at_least(m), C = (n + N - 1) / N;
   const double lg = (double)pa_log2(N), R = (double)batch * (double)C;
-  const double direct = PE_DIRECT_FLOOR_US + (double)batch * (double)n * (double)m / PE_DIRECT_PRODUCTS_PER_US;
-  const double tree = PE_TREE_US_PER_LEVEL * lg + ((double)N * lg * lg + 3.0 * R * (double)N * lg) / PE_TREE_ELEMENTS_PER_US +
-                      PE_TREE_US_PER_ROW * R;
+  const double direct = k.direct_floor_us + (double)batch * (double)n * (double)m / k.direct_products_per_us;
+  const double tree = k.tree_us_per_level * lg + ((double)N * lg * lg + 3.0 * R * (double)N * lg) / k.tree_elements_per_us +
+                      k.tree_us_per_row * R;
   return direct <= tree;
 }
+inline bool pe_direct_preferred(uint64_t n, uint64_t m, uint64_t batch) { return pe_direct_preferred(PE_COST_MIMC, n, m, batch); }
 
 // Ops (evaluation only): eval_pow_table(xs, m, lgS, tbl), eval_direct(PeDirect, coefs, tbl, dst) (dst[b][w][i]: the workgroup sums,
 //      canonical when W = 1), eval_sum(PeDirect, part, out), eval_chunks(coefs, n, batch, N, C, dst) ([batch C][N] rows of
 //      pe_chunk_rev_item), bcast_mul(a, b, rows, len) (a[r][i] *= b[i]), eval_combine(leaves, xs, m, N, C, batch, out)
-template <class Ops>
-int pa_eval_direct(Ops& o, const fp* coefs, uint64_t n, uint64_t batch, const fp* xs, uint64_t m, fp* out) {
-  const PeDirect s = pe_direct_shape(n, m, batch);
-  fp *tbl, *part = out;
+// The element type E is deduced from the pointers, as for the drivers above (fp: api_poly.hip, fpm: api_modpoly.hip).
+template <class Ops, class E>
+int pa_eval_direct(Ops& o, const typename pa_id<E>::type* coefs, uint64_t n, uint64_t batch, const E* xs, uint64_t m, E* out) {
+  const PeDirect s = pe_direct_shape_of<pe_group<E>::value>(n, m, batch);
+  E *tbl, *part = out;
   PA_TRY(o.buf(PA_BUF_1, (s.lgS + 1) * m, &tbl));
   if (s.W > 1) PA_TRY(o.buf(PA_BUF_2, batch * s.W * m, &part));
   PA_TRY(o.eval_pow_table(xs, m, s.lgS, tbl));
@@ -424,18 +436,18 @@ int pa_eval_direct(Ops& o, const fp* coefs, uint64_t n, uint64_t batch, const fp
   return s.W > 1 ? o.eval_sum(s, part, out) : 0;
 }
 
-template <class Ops>
-int pa_eval_tree(Ops& o, const fp* coefs, uint64_t n, uint64_t batch, const fp* xs, uint64_t m, fp* out) {
+template <class Ops, class E>
+int pa_eval_tree(Ops& o, const typename pa_id<E>::type* coefs, uint64_t n, uint64_t batch, const E* xs, uint64_t m, E* out) {
   const uint64_t N = pa_pow2_at_least(m), C = (n + N - 1) / N, R = batch * C;
   const uint32_t lg = pa_log2(N);
-  fp *tree, *hat, *t1, *t2, *rows, *r;
+  E *tree, *hat, *t1, *t2, *rows, *r;
   PA_TRY(o.buf(PA_BUF_TREE, (lg + 1) * N, &tree));
   PA_TRY(o.buf(PA_BUF_3, 2 * N, &hat));  // the tree's transforms, then the descent's zt
   PA_TRY(o.buf(PA_BUF_1, R * N > 2 * N ? R * N : 2 * N, &t1));
   PA_TRY(o.buf(PA_BUF_2, 2 * N, &t2));
   PA_TRY(o.buf(PA_BUF_4, 2 * R * N, &rows));  // the rows' root products, then the descent's transforms
   PA_TRY(o.buf(PA_BUF_5, 2 * N + 2 * R * N, &r));
-  fp *g = r, *rz = r + N, *d0 = r + 2 * N, *d1 = d0 + R * N;
+  E *g = r, *rz = r + N, *d0 = r + 2 * N, *d1 = d0 + R * N;
   PA_TRY(pa_tree_up(o, xs, m, N, tree, true, hat));
   PA_TRY(pa_cp(o, pa_level(tree, N, lg, true), rz, 1, N, 0, 0, N, (int64_t)N, -1, PA_ONE_AT_END));  // rev(Z) mod y^N
   PA_TRY(pa_inverse(o, rz, N, N, g, t1, t2));
@@ -445,14 +457,14 @@ int pa_eval_tree(Ops& o, const fp* coefs, uint64_t n, uint64_t batch, const fp* 
   PA_TRY(o.bcast_mul(rows, t2, R, 2 * N));
   PA_TRY(o.ntt(rows, rows, R, 2 * N, 0, true));
   PA_TRY(pa_cp(o, rows, d0, R, N, 2 * N, N, 2 * N, 0, 1, 0));  // D: the low N coefficients of each row
-  fp* leaves = nullptr;
+  E* leaves = nullptr;
   PA_TRY(pa_descend(o, tree, N, R, d0, d1, t1, t2, rows, hat, &leaves));
   return o.eval_combine(leaves, xs, m, N, C, batch, out);
 }
 
 // out[b][i] = sum_k coefs[b][k] x_i^k, canonical, for b < batch, i < m (n = 0: zeros)
-template <class Ops>
-int pa_eval(Ops& o, const fp* coefs, uint64_t n, uint64_t batch, const fp* xs, uint64_t m, fp* out, bool direct) {
+template <class Ops, class E>
+int pa_eval(Ops& o, const typename pa_id<E>::type* coefs, uint64_t n, uint64_t batch, const E* xs, uint64_t m, E* out, bool direct) {
   if (m == 0) return 0;
   if (n == 0) return pa_cp(o, nullptr, out, 1, batch * m, 0, 0, 0, 0, 1, 0);
   return direct ? pa_eval_direct(o, coefs, n, batch, xs, m, out) : pa_eval_tree(o, coefs, n, batch, xs, m, out);

@@ -9,6 +9,7 @@
     multi_inv_wire(data) -> bytes, multi_interp_4_wire(xs, ys, rows) -> bytes,
     zpoly_wire(xs) -> bytes, lagrange_interp_wire(xs, ys) -> bytes   (wire form in and out, for large inputs)
     mod_multi_inv_wire(p, data), mod_multi_interp_4_wire(p, xs, ys, rows), mod_zpoly_wire(p, xs), mod_lagrange_interp_wire(p, xs, ys)
+    (and polynomial.mod_eval_wire(p, coefs, xs, batch))
                                                        (the same over any prime p < 2^256: sh_mod_*, always on the device)
 
 For the MiMC prime they always run on the GPU through libstarkhip.so (sh_multi_inv, sh_multi_interp_4) and raise when the library
@@ -234,12 +235,34 @@ def lagrange_interp(field, xs, ys):
     return polys_over(WireList(lagrange_interp_wire(_lib.to_wire(xs), _lib.to_wire(ys)), field))
 
 
+# multi_eval over another prime field makes one sh_mod_poly_eval call from this many coefficients x points on (and at least one of
+# each), under _lib.mod_poly_routable with no transform requirement: the smallest power of two from which the device call won end to
+# end at every larger measured size (tools/mod_poly_eval_time.py over BN254 against the host loop on the same inputs in the same run,
+# profiles/r22_mod_poly_eval.json, "routing": at 8 points 0.109 ms against 0.128 ms for n m = 128 and 0.106 against 0.066 ms for 64; on
+# square shapes 0.116 against 0.254 ms for 256 and 0.110 against 0.066 ms for 64).
+MOD_EVAL_DEVICE_MIN_WORK = 128
+_EVAL_MAX_COEFS, _EVAL_MAX_POINTS = 1 << 25, 1 << 20
+
+
+def _mod_eval_on_device(field, n, m):
+    p = getattr(field, "p", None)
+    if p is None or not 0 < n <= _EVAL_MAX_COEFS or not 0 < m <= _EVAL_MAX_POINTS or n * m < MOD_EVAL_DEVICE_MIN_WORK:
+        return False
+    return _lib.mod_poly_routable(p, None, n)
+
+
 def multi_eval(field, poly, xs):
     """Polynomial.__call__ (polynomial.py:158-164) at every x of xs: for the MiMC field one sh_poly_eval call, a WireList of the
-    field's elements (raises without a device, like multi_inv); for any other ring poly(x) per point on the host, a list.  poly is a
-    Polynomial or a sequence of coefficients (constant first)."""
+    field's elements (raises without a device, like multi_inv); for another prime field one sh_mod_poly_eval call and a WireList when
+    _mod_eval_on_device holds; for any other ring or size poly(x) per point on the host, a list.  poly is a Polynomial or a sequence
+    of coefficients (constant first)."""
     coefficients = poly.coefficients if hasattr(poly, "coefficients") else list(poly)
     if not _on_device(field):
+        xs = list(xs)
+        if _mod_eval_on_device(field, len(coefficients), len(xs)) and all(isinstance(x, (int, field)) and not isinstance(x, bool) for x in xs):
+            from .polynomial import mod_eval_wire
+            p = int(field.p)
+            return WireList(mod_eval_wire(p, _lib.to_wire(coefficients, p), _lib.to_wire(xs, p)), field)
         p = poly if callable(poly) else polynomials_over(field)(coefficients)
         return [p(x) for x in xs]
     from .polynomial import eval_wire

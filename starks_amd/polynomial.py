@@ -5,7 +5,8 @@ its `typecheck` does (numbertype.py:31-54).
 Over the MiMC field every product and division runs on the GPU at every size (sh_poly_mul, sh_poly_divmod: NTT products and a
 Newton inverse, O(n log n)); the result is backed by the device's bytes (a WireList, trailing zeros stripped on the bytes).  Calling
 such a device-backed polynomial at an int or field element runs sh_poly_eval from EVAL_DEVICE_MIN_COEFS coefficients on, when the
-process already holds a device context; every other call is the reference's loop.  Over another PRIME field products and
+process already holds a device context; every other call is the reference's loop.  Over another PRIME field __call__ goes to
+sh_mod_poly_eval from MOD_EVAL_DEVICE_MIN_COEFS coefficients on (a list of elements is converted), and products and
 divisions go to the device's generic entries (sh_mod_poly_mul, sh_mod_poly_divmod; mod_mul_wire and mod_divmod_wire always do) when
 the process already holds a context, the field's 2-adicity admits the call's transforms and the operands reach the measured threshold
 (MOD_DEVICE_MIN).  Any other ring or size (the reference's own tests use Z/5, Z/7, Z/11 and Fraction) runs the reference's schoolbook
@@ -80,6 +81,9 @@ def polynomials_over(ring):
         def __call__(self, x):  # polynomial.py:158-164
             if _eval_on_device(ring, self.coefficients, x):
                 return WireList(eval_wire(_lib_mod().to_wire(self.coefficients), _lib_mod().to_wire([x])), ring)[0]
+            if _mod_eval_on_device(ring, self.coefficients, x):
+                p, to_wire = int(ring.p), _lib_mod().to_wire
+                return WireList(mod_eval_wire(p, to_wire(self.coefficients, p), to_wire([x], p)), ring)[0]
             y = ring(0)
             pw = ring(1)
             for a in self.coefficients:
@@ -227,6 +231,26 @@ def _on_device(ring):
     return int(getattr(ring, "p", 0)) == MIMC_P
 
 
+# Another prime field: __call__ at an int or element goes to the device (sh_mod_poly_eval) from this many coefficients on, under
+# _lib.mod_poly_routable with no transform requirement (the direct path runs none, so the field's 2-adicity does not matter).  Unlike
+# the MiMC rule the coefficients need not be a WireList: converting a list of n elements to wire form costs 0.4 us per element
+# against the host loop's 2.2 us per coefficient (two ring operations), measured on the host at n = 2^16 over BN254, so the conversion
+# never decides.  The threshold is the smallest power of two from which the device call won end to end at every larger measured size
+# (tools/mod_poly_eval_time.py over BN254 against the loop of __call__ on the same inputs in the same run,
+# profiles/r22_mod_poly_eval.json, "routing": 0.082 ms against 0.139 ms at 128 coefficients, 0.077 against 0.066 ms at 64; at 2^20
+# coefficients 1.44 ms against 1.48 s).
+MOD_EVAL_DEVICE_MIN_COEFS = 128
+
+
+def _mod_eval_on_device(ring, coefficients, x):
+    p = getattr(ring, "p", None)
+    if p is None or not MOD_EVAL_DEVICE_MIN_COEFS <= len(coefficients) <= _EVAL_MAX_COEFS:
+        return False
+    if not (isinstance(x, ring) or (isinstance(x, int) and not isinstance(x, bool))):
+        return False
+    return _lib_mod().mod_poly_routable(p, None, len(coefficients))
+
+
 # Another prime field: products and divisions go to the device (sh_mod_poly_mul, sh_mod_poly_divmod) when _lib.mod_poly_routable holds
 # and the SHORTER side of the work -- min(n_a, n_b) of a product, min(n_a - n_b + 1, n_b) (quotient and divisor lengths) of a division --
 # has at least this many coefficients; None: routing is off for the operation.  The host loops cost n_a n_b and (n_a - n_b + 1) n_b
@@ -312,6 +336,23 @@ def eval_wire(coefs, xs, batch=1):
         return b""
     out = ctypes.create_string_buffer(32 * batch * m)
     _lib.check(_lib.lib().sh_poly_eval(_lib.ctx(), coefs if n else None, n, batch, xs, m, out), "sh_poly_eval")
+    return out.raw
+
+
+def mod_eval_wire(modulus, coefs, xs, batch=1, root=None):
+    """eval_wire over any prime modulus below 2^256 (sh_mod_poly_eval): [batch][n] coefficients at m points -> [batch][m] canonical
+    values, wire form in and out; root = (root of unity, log2 of its order), default _lib.two_adic_root(modulus) -- the direct path
+    needs none, (1, 0) is valid.  Always on the device."""
+    from . import _lib
+    coefs, xs = _as_bytes(coefs), _as_bytes(xs)
+    if batch < 1 or (len(coefs) // 32) % batch:
+        raise ValueError("coefs must hold batch polynomials of the same length")
+    n, m = len(coefs) // 32 // batch, len(xs) // 32
+    if m == 0:
+        return b""
+    mod, w, k = _lib.mod_poly_args(modulus, root)
+    out = ctypes.create_string_buffer(32 * batch * m)
+    _lib.check(_lib.lib().sh_mod_poly_eval(_lib.ctx(), mod, w, k, coefs if n else None, n, batch, xs, m, out), "sh_mod_poly_eval")
     return out.raw
 
 
