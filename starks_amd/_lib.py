@@ -163,6 +163,18 @@ def lib():
         "sh_mod_lagrange_interp": (i32, [c_p, u8p, u8p, u32, u8p, u8p, u64, c_p]),
         "sh_dev_mod_poly_eval": (i32, [c_p, u8p, u8p, u32, c_p, u64, u32, c_p, u64, c_p]),
         "sh_mod_poly_eval": (i32, [c_p, u8p, u8p, u32, u8p, u64, u32, u8p, u64, c_p]),
+        "sh_dev_mod64_multi_inv": (i32, [c_p, u64, c_p, c_p, u64]),
+        "sh_mod64_multi_inv": (i32, [c_p, u64, c_p, u64, c_p]),
+        "sh_dev_mod64_multi_interp_4": (i32, [c_p, u64, c_p, c_p, u64, c_p]),
+        "sh_mod64_multi_interp_4": (i32, [c_p, u64, c_p, c_p, u64, c_p]),
+        "sh_dev_mod64_poly_mul": (i32, [c_p, u64, u64, u32, c_p, u64, c_p, u64, c_p]),
+        "sh_mod64_poly_mul": (i32, [c_p, u64, u64, u32, c_p, u64, c_p, u64, c_p]),
+        "sh_dev_mod64_poly_divmod": (i32, [c_p, u64, u64, u32, c_p, u64, c_p, u64, c_p, c_p]),
+        "sh_mod64_poly_divmod": (i32, [c_p, u64, u64, u32, c_p, u64, c_p, u64, c_p, c_p]),
+        "sh_dev_mod64_zpoly": (i32, [c_p, u64, u64, u32, c_p, u64, c_p]),
+        "sh_mod64_zpoly": (i32, [c_p, u64, u64, u32, c_p, u64, c_p]),
+        "sh_dev_mod64_lagrange_interp": (i32, [c_p, u64, u64, u32, c_p, c_p, u64, c_p]),
+        "sh_mod64_lagrange_interp": (i32, [c_p, u64, u64, u32, c_p, c_p, u64, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares
@@ -372,6 +384,15 @@ def mod_poly_args(modulus, root=None):
     m = int(modulus)
     w, k = two_adic_root(m) if root is None else root
     return m.to_bytes(32, "big"), (int(w) % m).to_bytes(32, "big"), int(k)
+
+
+def mod64_poly_args(modulus, root=None):
+    """(modulus, root, root_log) of a sh_mod64_poly_* call, plain ints; root = None: two_adic_root(modulus), else (root, root_log)"""
+    m = int(modulus)
+    if not 3 <= m < 1 << 64:
+        raise ValueError("the packed-word entries take a modulus in [3, 2^64)")
+    w, k = two_adic_root(m) if root is None else root
+    return m, int(w) % m, int(k)
 
 
 def mod_poly_routable(p, op, n_a, n_b=0):

@@ -324,3 +324,26 @@ hipError_t shk_me_chunks(const fpm* coefs, uint64_t n, uint64_t batch, uint64_t 
 hipError_t shk_me_bcast_mul(fpm* a, const fpm* b, uint64_t rows, uint64_t len, const fpm_mod& M, hipStream_t st);
 hipError_t shk_me_combine(const fpm* leaves, const fpm* xs, uint64_t m, uint64_t N, uint64_t C, uint64_t batch, fpm* out, const fpm_mod& M,
                           hipStream_t st);
+
+// ---- mod64poly.hip: polynomial arithmetic and batch inversion over any prime modulus below 2^64 on packed 64-bit words
+// (mod64poly_items.cuh; every array holds PLAIN words, the modulus block is an argument of every launch).  The pointwise product of two
+// transforms is shk_n64_pointwise ------------------------------------------------------------------------------------------------------
+hipError_t shk_m6p_copy(const PaCopy& c, const uint64_t* src, uint64_t* dst, const f64_mod& M, hipStream_t st);
+// log2d >= 1 (rows of 2d >= 2 words)
+hipError_t shk_m6p_tree(const uint64_t* hz, uint64_t* oz, const uint64_t* hn, uint64_t* on, uint32_t log2d, uint64_t nodes,
+                        const f64_mod& M, hipStream_t st);
+hipError_t shk_m6p_mid(const uint64_t* hd, uint64_t* hr, uint32_t log2d, uint64_t children, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6p_newton(const uint64_t* F, uint64_t* G, uint64_t n, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6p_inv1(const uint64_t* src, uint64_t* dst, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6p_deriv_rev(const uint64_t* top, uint64_t* out, uint64_t N, uint64_t n, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6p_weights(const uint64_t* ys, const uint64_t* inv, uint64_t* out, uint64_t n, uint64_t N, const f64_mod& M,
+                           hipStream_t st);
+hipError_t shk_m6p_sub(const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n, const f64_mod& M, hipStream_t st);
+// scratch: words of the levels above the items (0 when they fit one tile)
+uint64_t shk_m6p_multi_inv_scratch(uint64_t n);
+uint64_t shk_m6p_multi_interp_4_scratch(uint64_t rows);
+// out[i] = in[i]^-1, 0 for in[i] == 0 mod p; in may equal out; n >= 1
+hipError_t shk_m6p_multi_inv(const uint64_t* in, uint64_t* out, uint64_t n, uint64_t* scratch, const f64_mod& M, hipStream_t st);
+// xs, ys, coeffs: [rows][4]; coeffs may equal xs or ys; rows >= 1
+hipError_t shk_m6p_multi_interp_4(const uint64_t* xs, const uint64_t* ys, uint64_t* coeffs, uint64_t rows, uint64_t* scratch,
+                                  const f64_mod& M, hipStream_t st);

@@ -111,6 +111,67 @@ def mod_lagrange_interp_wire(modulus, xs, ys, root=None):
     return out.raw
 
 
+def mod64_multi_inv_words(modulus, data):
+    """multi_inv over any prime modulus below 2^64 on packed 64-bit words (sh_mod64_multi_inv): native 8-byte words (a list of ints,
+    bytes or any buffer of words; any 64-bit values) -> their inverses mod p, canonical, 0 for a word == 0 mod p; a memoryview of
+    format 'Q' over a fresh bytearray.  An entry of its own: multi_inv keeps the 32-byte path.  Always on the device."""
+    from .fft import _word_result, _words
+    src, _keep, n = _words(data)
+    if n == 0:
+        return memoryview(bytearray()).cast("Q")
+    out, dst = _word_result(n)
+    _lib.check(_lib.lib().sh_mod64_multi_inv(_lib.ctx(), _lib.mod64_poly_args(modulus, (1, 0))[0], src, n, dst), "sh_mod64_multi_inv")
+    del dst
+    return memoryview(out).cast("Q")
+
+
+def mod64_multi_interp_4_words(modulus, xs, ys):
+    """multi_interp_4 over any prime modulus below 2^64 on packed words (sh_mod64_multi_interp_4): xs, ys = [rows][4] words ->
+    [rows][4] coefficient words, operands and result as in `mod64_multi_inv_words`.  Always on the device."""
+    from .fft import _word_result, _words
+    sx, _kx, nx = _words(xs)
+    sy, _ky, ny = _words(ys)
+    if nx != ny or nx % 4:
+        raise ValueError("xs and ys must hold 4 * rows words each")
+    if nx == 0:
+        return memoryview(bytearray()).cast("Q")
+    out, dst = _word_result(nx)
+    _lib.check(_lib.lib().sh_mod64_multi_interp_4(_lib.ctx(), _lib.mod64_poly_args(modulus, (1, 0))[0], sx, sy, nx // 4, dst),
+               "sh_mod64_multi_interp_4")
+    del dst
+    return memoryview(out).cast("Q")
+
+
+def mod64_zpoly_words(modulus, xs, root=None):
+    """zpoly over any prime modulus below 2^64 on packed words (sh_mod64_zpoly): n words -> the n + 1 coefficients of
+    prod (X - x_i), leading 1 included; root = (root of unity, log2 of its order), default _lib.two_adic_root(modulus).  Always on
+    the device."""
+    from .fft import _word_result, _words
+    sx, _kx, n = _words(xs)
+    m, w, k = _lib.mod64_poly_args(modulus, root)
+    out, dst = _word_result(n + 1)
+    _lib.check(_lib.lib().sh_mod64_zpoly(_lib.ctx(), m, w, k, sx if n else None, n, dst), "sh_mod64_zpoly")
+    del dst
+    return memoryview(out).cast("Q")
+
+
+def mod64_lagrange_interp_words(modulus, xs, ys, root=None):
+    """lagrange_interp over any prime modulus below 2^64 on packed words (sh_mod64_lagrange_interp), repeated x's included: n + n
+    words -> n coefficient words.  Always on the device."""
+    from .fft import _word_result, _words
+    sx, _kx, n = _words(xs)
+    sy, _ky, ny = _words(ys)
+    if n != ny:
+        raise ValueError("xs and ys must hold the same number of words")
+    if n == 0:
+        return memoryview(bytearray()).cast("Q")
+    m, w, k = _lib.mod64_poly_args(modulus, root)
+    out, dst = _word_result(n)
+    _lib.check(_lib.lib().sh_mod64_lagrange_interp(_lib.ctx(), m, w, k, sx, sy, n, dst), "sh_mod64_lagrange_interp")
+    del dst
+    return memoryview(out).cast("Q")
+
+
 def multi_inv_wire(data):
     """n 32-byte big-endian values (may be >= p) -> their n inverses, canonical, 0 for a value == 0 mod p (sh_multi_inv)."""
     data = bytes(data) if not isinstance(data, bytes) else data

@@ -303,6 +303,43 @@ def mod_divmod_wire(modulus, a, b, root=None):
     return q.raw[:32 * nq], r.raw[:32 * nr]
 
 
+def mod64_mul_words(modulus, a, b, root=None):
+    """The exact product over any prime modulus below 2^64 on packed 64-bit words (sh_mod64_poly_mul): a, b = native 8-byte words (a
+    list of ints, bytes or any buffer of words; any 64-bit values) -> len(a) + len(b) - 1 canonical coefficients, a memoryview of
+    format 'Q' over a fresh bytearray (empty when either operand is).  root = (root of unity, log2 of its order), default
+    _lib.two_adic_root(modulus).  An entry of its own: Polynomial.__mul__ keeps the 32-byte path.  Always on the device."""
+    from . import _lib
+    from .fft import _word_result, _words
+    sa, _ka, na = _words(a)
+    sb, _kb, nb = _words(b)
+    if na == 0 or nb == 0:
+        return memoryview(bytearray()).cast("Q")
+    m, w, k = _lib.mod64_poly_args(modulus, root)
+    out, dst = _word_result(na + nb - 1)
+    _lib.check(_lib.lib().sh_mod64_poly_mul(_lib.ctx(), m, w, k, sa, na, sb, nb, dst), "sh_mod64_poly_mul")
+    del dst
+    return memoryview(out).cast("Q")
+
+
+def mod64_divmod_words(modulus, a, b, root=None):
+    """(quotient, remainder) over any prime modulus below 2^64 on packed 64-bit words (sh_mod64_poly_divmod), operands and results as
+    in `mod64_mul_words`: len(a) - len(b) + 1 and len(b) - 1 words, or no quotient and a itself for len(a) < len(b).  Always on the
+    device."""
+    from . import _lib
+    from .fft import _word_result, _words
+    sa, _ka, na = _words(a)
+    sb, _kb, nb = _words(b)
+    if nb == 0:
+        raise ZeroDivisionError
+    nq, nr = max(na - nb + 1, 0), min(na, nb - 1)
+    m, w, k = _lib.mod64_poly_args(modulus, root)
+    q, dq = _word_result(max(nq, 1))
+    r, dr = _word_result(max(nr, 1))
+    _lib.check(_lib.lib().sh_mod64_poly_divmod(_lib.ctx(), m, w, k, sa if na else None, na, sb, nb, dq, dr), "sh_mod64_poly_divmod")
+    del dq, dr
+    return memoryview(q).cast("Q")[:nq], memoryview(r).cast("Q")[:nr]
+
+
 def _as_bytes(data):
     data = bytes(data) if not isinstance(data, bytes) else data
     if len(data) % 32:
