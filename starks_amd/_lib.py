@@ -175,6 +175,8 @@ def lib():
         "sh_mod64_zpoly": (i32, [c_p, u64, u64, u32, c_p, u64, c_p]),
         "sh_dev_mod64_lagrange_interp": (i32, [c_p, u64, u64, u32, c_p, c_p, u64, c_p]),
         "sh_mod64_lagrange_interp": (i32, [c_p, u64, u64, u32, c_p, c_p, u64, c_p]),
+        "sh_dev_mod64_poly_eval": (i32, [c_p, u64, u64, u32, c_p, u64, u32, c_p, u64, c_p]),
+        "sh_mod64_poly_eval": (i32, [c_p, u64, u64, u32, c_p, u64, u32, c_p, u64, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export what the header declares

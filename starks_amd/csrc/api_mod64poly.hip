@@ -1,8 +1,10 @@
-// api_mod64poly.hip -- polynomial products, division, zpoly, lagrange_interp, batch inversion and four-point interpolation over any prime
-// modulus below 2^64 on packed 64-bit words, on the host side: the drivers of poly_items.cuh over the packed-word transform
-// (api_ntt64.hip: mod64_table, mod64_run) and the kernels of mod64poly.hip.  Every check runs here before the first launch; every error
+// api_mod64poly.hip -- polynomial products, division, zpoly, lagrange_interp, batch inversion, four-point interpolation and evaluation
+// at arbitrary points (sh_mod64_poly_eval) over any prime modulus below 2^64 on packed 64-bit words, on the host side: the drivers of
+// poly_items.cuh over the packed-word transform (api_ntt64.hip: mod64_table, mod64_run) and the kernels of mod64poly.hip and
+// mod64eval.hip.  Every check runs here before the first launch; every error
 // text opens with the entry's name.
 #include "ctx.hpp"
+#include "mod64eval_items.cuh"
 #include "mod64poly_items.cuh"
 #include "modpoly_items.cuh"  // mp_max_transform: the one statement of the largest transform
 using namespace shk;
@@ -115,6 +117,27 @@ struct Mod64Ops {
     return SH_OK;
   }
   int sub(const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n) { HIP_TRY(c, shk_m6p_sub(a, b, out, n, M, c->stream)); return SH_OK; }
+  int eval_pow_table(const uint64_t* xs, uint64_t m, uint32_t lgS, uint64_t* tbl) {
+    HIP_TRY(c, shk_m6e_pow_table(xs, m, lgS, tbl, M, c->stream));
+    return SH_OK;
+  }
+  int eval_direct(const PeDirect& s, const uint64_t* coefs, const uint64_t* tbl, uint64_t* dst) {
+    HIP_TRY(c, shk_m6e_direct(s, coefs, tbl, dst, M, c->stream));
+    return SH_OK;
+  }
+  int eval_sum(const PeDirect& s, const uint64_t* part, uint64_t* out) { HIP_TRY(c, shk_m6e_sum(s, part, out, M, c->stream)); return SH_OK; }
+  int eval_chunks(const uint64_t* coefs, uint64_t n, uint64_t batch, uint64_t N, uint64_t C, uint64_t* dst) {
+    HIP_TRY(c, shk_m6e_chunks(coefs, n, batch, N, C, dst, c->stream));
+    return SH_OK;
+  }
+  int bcast_mul(uint64_t* a, const uint64_t* b, uint64_t rows, uint64_t len) {
+    HIP_TRY(c, shk_m6e_bcast_mul(a, b, rows, len, M, c->stream));
+    return SH_OK;
+  }
+  int eval_combine(const uint64_t* leaves, const uint64_t* xs, uint64_t m, uint64_t N, uint64_t C, uint64_t batch, uint64_t* out) {
+    HIP_TRY(c, shk_m6e_combine(leaves, xs, m, N, C, batch, out, M, c->stream));
+    return SH_OK;
+  }
   int buf(int slot, uint64_t elems, uint64_t** out) { return ws(sh_ctx::WS_PA_TREE + slot, elems, out); }
   int ws(int slot, uint64_t elems, uint64_t** out) {
     void* p = nullptr;
@@ -151,6 +174,27 @@ int point_sizes(sh_ctx* c, const char* who, uint64_t n) {
 }
 const uint64_t* cw(const void* p) { return static_cast<const uint64_t*>(p); }
 uint64_t* w(void* p) { return static_cast<uint64_t*>(p); }
+
+// sh_mod64_poly_eval's limits and checks (sh_mod_poly_eval's: api_modpoly.hip), the modulus and the root, then the path:
+// STARKHIP_EVAL_PATH, else the direct path when the tree's transform exceeds the root's order, else mod64eval_items.cuh's cost rule.
+// A forced tree that does not fit is refused here, before any launch.
+constexpr uint64_t M6E_MAX_COEFS = 1ull << 25, M6E_MAX_TOTAL = 1ull << 26;
+int eval_check(sh_ctx* c, const char* who, Mod64Ops* o, uint64_t modulus, uint64_t root, uint32_t root_log, const void* coefs, uint64_t n,
+               uint32_t batch, const void* xs, uint64_t m, const void* out, bool* direct) {
+  if (batch == 0) return fail(c, who, "batch is zero", SH_ERR_INVALID);
+  if ((n && !coefs) || (m && (!xs || !out))) return fail(c, who, "null pointer", SH_ERR_INVALID);
+  if (n > M6E_MAX_COEFS) return fail(c, who, "a polynomial is limited to 2^25 coefficients", SH_ERR_UNSUPPORTED);
+  if ((uint64_t)batch * n > M6E_MAX_TOTAL) return fail(c, who, "the polynomials are limited to 2^26 coefficients in all", SH_ERR_UNSUPPORTED);
+  if (m > M6P_MAX_POINTS) return fail(c, who, "the points are limited to 2^20", SH_ERR_UNSUPPORTED);
+  const uint64_t out_bytes = 8ull * batch * m;
+  if (any_overlap(out, out_bytes, coefs, 8ull * batch * n) || any_overlap(out, out_bytes, xs, 8 * m))
+    return fail(c, who, "the output overlaps an input", SH_ERR_INVALID);
+  SH_TRY(o->init(c, who, modulus, root, root_log));
+  const int forced = shk_knobs().eval_path;
+  *direct = forced ? forced == 1 : m6e_direct_preferred(n, m, batch, root_log);
+  if (!*direct) SH_TRY(o->fits(who, mp_max_transform(MP_OP_EVAL, n, m)));
+  return SH_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -371,5 +415,34 @@ int sh_mod64_lagrange_interp(sh_ctx* c, uint64_t modulus, uint64_t root, uint32_
   SH_TRY(o.ws(sh_ctx::WS_MISC, n, &d_out));
   SH_TRY(pa_lagrange(o, cw(x), cw(y), n, d_out));
   return o.download(d_out, out, n);
+}
+
+int sh_dev_mod64_poly_eval(sh_ctx* c, uint64_t modulus, uint64_t root, uint32_t root_log, const void* d_coefs, uint64_t n, uint32_t batch,
+                           const void* d_xs, uint64_t m, void* d_out) {
+  static const char who[] = "sh_dev_mod64_poly_eval";
+  if (!c) return SH_ERR_INVALID;
+  Mod64Ops o;
+  bool direct = true;
+  SH_TRY(eval_check(c, who, &o, modulus, root, root_log, d_coefs, n, batch, d_xs, m, d_out, &direct));
+  if (m == 0) return SH_OK;
+  SH_TRY(enter(c));
+  return pa_eval(o, cw(d_coefs), n, batch, cw(d_xs), m, w(d_out), direct);
+}
+
+int sh_mod64_poly_eval(sh_ctx* c, uint64_t modulus, uint64_t root, uint32_t root_log, const uint64_t* coefs, uint64_t n, uint32_t batch,
+                       const uint64_t* xs, uint64_t m, uint64_t* out) {
+  static const char who[] = "sh_mod64_poly_eval";
+  if (!c) return SH_ERR_INVALID;
+  Mod64Ops o;
+  bool direct = true;
+  SH_TRY(eval_check(c, who, &o, modulus, root, root_log, coefs, n, batch, xs, m, out, &direct));
+  if (m == 0) return SH_OK;
+  SH_TRY(enter(c));
+  uint64_t *x = nullptr, *d_xs, *d_out;
+  if (n) SH_TRY(o.upload(coefs, (uint64_t)batch * n, sh_ctx::WS_X, &x));
+  SH_TRY(o.upload(xs, m, sh_ctx::WS_Y, &d_xs));
+  SH_TRY(o.ws(sh_ctx::WS_MISC, (uint64_t)batch * m, &d_out));
+  SH_TRY(pa_eval(o, cw(x), n, batch, cw(d_xs), m, d_out, direct));
+  return o.download(d_out, out, (uint64_t)batch * m);
 }
 }  // extern "C"

@@ -347,3 +347,17 @@ hipError_t shk_m6p_multi_inv(const uint64_t* in, uint64_t* out, uint64_t n, uint
 // xs, ys, coeffs: [rows][4]; coeffs may equal xs or ys; rows >= 1
 hipError_t shk_m6p_multi_interp_4(const uint64_t* xs, const uint64_t* ys, uint64_t* coeffs, uint64_t rows, uint64_t* scratch,
                                   const f64_mod& M, hipStream_t st);
+
+// ---- mod64eval.hip: evaluation at arbitrary points over any prime modulus below 2^64 on packed 64-bit words (mod64eval_items.cuh;
+// poly_items.cuh: pa_eval_direct, pa_eval_tree).  Plain words everywhere but tbl, which holds Montgomery forms ---------------------------
+// tbl[b m + i] = x_i^(2^b) R, b <= lgS
+hipError_t shk_m6e_pow_table(const uint64_t* xs, uint64_t m, uint32_t lgS, uint64_t* tbl, const f64_mod& M, hipStream_t st);
+// dst[b][w][i]: workgroup w's sum for point i of polynomial b, canonical; coefs [batch][n], any 64-bit values
+hipError_t shk_m6e_direct(const PeDirect& s, const uint64_t* coefs, const uint64_t* tbl, uint64_t* dst, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6e_sum(const PeDirect& s, const uint64_t* part, uint64_t* out, const f64_mod& M, hipStream_t st);
+// N a power of two, at least 2; dst 16-byte aligned (a workspace buffer)
+hipError_t shk_m6e_chunks(const uint64_t* coefs, uint64_t n, uint64_t batch, uint64_t N, uint64_t C, uint64_t* dst, hipStream_t st);
+// len even; a and b 16-byte aligned (workspace buffers)
+hipError_t shk_m6e_bcast_mul(uint64_t* a, const uint64_t* b, uint64_t rows, uint64_t len, const f64_mod& M, hipStream_t st);
+hipError_t shk_m6e_combine(const uint64_t* leaves, const uint64_t* xs, uint64_t m, uint64_t N, uint64_t C, uint64_t batch, uint64_t* out,
+                           const f64_mod& M, hipStream_t st);

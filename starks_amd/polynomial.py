@@ -340,6 +340,28 @@ def mod64_divmod_words(modulus, a, b, root=None):
     return memoryview(q).cast("Q")[:nq], memoryview(r).cast("Q")[:nr]
 
 
+def mod64_eval_words(modulus, coefs, xs, batch=1, root=None):
+    """The values of `batch` polynomials of n coefficients each ([batch][n], ascending) at the m points xs over any prime modulus
+    below 2^64 on packed 64-bit words (sh_mod64_poly_eval), operands as in `mod64_mul_words` -> [batch][m] canonical words, a
+    memoryview of format 'Q' (empty for m = 0): out[b][i] = sum_k coefs[b][k] xs[i]^k.  n = 0 gives zeros.  root as there -- the
+    direct path needs none, (1, 0) is valid.  An entry of its own: Polynomial.__call__ and multi_eval keep the 32-byte path.  Always
+    on the device."""
+    from . import _lib
+    from .fft import _word_result, _words
+    sc, _kc, nc = _words(coefs)
+    sx, _kx, m = _words(xs)
+    if batch < 1 or nc % batch:
+        raise ValueError("coefs must hold batch polynomials of the same length")
+    if m == 0:
+        return memoryview(bytearray()).cast("Q")
+    n = nc // batch
+    p, w, k = _lib.mod64_poly_args(modulus, root)
+    out, dst = _word_result(batch * m)
+    _lib.check(_lib.lib().sh_mod64_poly_eval(_lib.ctx(), p, w, k, sc if n else None, n, batch, sx, m, dst), "sh_mod64_poly_eval")
+    del dst
+    return memoryview(out).cast("Q")
+
+
 def _as_bytes(data):
     data = bytes(data) if not isinstance(data, bytes) else data
     if len(data) % 32:
