@@ -223,6 +223,35 @@ __host__ __device__ constexpr uint32_t tw_lds_slot(uint32_t ex, uint32_t c) {
   const uint32_t k = tw_lds_key(ex);
   return ((((ex & ~3u) | (k & 3u)) << 2) | (c ^ (k >> 2)));
 }
+// THE ADDRESS OF A PAIR, in bytes from the start of the table region.  tw_lds_slot is linear over GF(2) in the exponent (the key is
+// XORs of shifts under a mask, and the ORs join disjoint bits), and so is the exponent in the row index.  The two butterflies of a
+// level differ in one level bit of the row index, which the row base has clear: the second pair's address is the first's XOR a
+// compile-time constant (zero where the level's mask drops that bit), and the chunks of a pair are its address XOR 16, 32, 48.  A
+// thread forms one address per level; every other read is one XOR by a constant, or an immediate offset where the bit is clear.
+template <int LOG_R, int g>
+__host__ __device__ constexpr uint32_t tile_tw_pair_xor(int b) {
+  return 16u * tw_lds_slot(tile_tw_exponent<LOG_R, g>(b, 0) ^ tile_tw_exponent<LOG_R, g>(b & ~1, 0), 0);
+}
+template <int LOG_R, int g>
+__host__ __device__ constexpr uint32_t tile_tw_byte(int b, uint32_t ibase, uint32_t c) {
+  return (16u * tw_lds_slot(tile_tw_exponent<LOG_R, g>(b & ~1, ibase), 0)) ^ tile_tw_pair_xor<LOG_R, g>(b) ^ (16u * c);
+}
+// What the kernel computes for butterfly b (compile-time).  The pair constant's bits above the key (8 and up) fall on bits the level's
+// address has clear: they are added, and end up in the read's immediate offset.  Its key bits 4, 5 only rotate the chunks: the second
+// pair reads the first pair's four addresses in another order, and the read is tile_tw_byte as it stands.  Key bits 6, 7 cost one XOR
+// for the pair: tile_tw_level folds the key bits into the level's address once, and tile_tw_read adds the rest per chunk.
+template <int LOG_R, int g, int b>
+__host__ __device__ constexpr bool tile_tw_keyed() { return (tile_tw_pair_xor<LOG_R, g>(b) & 0xc0u) != 0; }
+template <int LOG_R, int g, int b>
+__host__ __device__ constexpr uint32_t tile_tw_level(uint32_t ibase) {
+  const uint32_t at = tile_tw_byte<LOG_R, g>(b & ~1, ibase, 0);
+  return tile_tw_keyed<LOG_R, g, b>() ? at ^ (tile_tw_pair_xor<LOG_R, g>(b) & 0xf0u) : at;
+}
+template <int LOG_R, int g, int b>
+__host__ __device__ constexpr uint32_t tile_tw_read(uint32_t level, uint32_t ibase, uint32_t c) {
+  if constexpr (tile_tw_keyed<LOG_R, g, b>()) return (level ^ (16u * c)) + (tile_tw_pair_xor<LOG_R, g>(b) & ~0xffu);
+  else return tile_tw_byte<LOG_R, g>(b, ibase, c);
+}
 // the copy: thread tid of `threads` moves the chunks j = tid, tid + threads, ... < 2 R of a.wR (chunk j = pair j / 4, part j % 4)
 template <int LOG_R, int LOG_T>
 __host__ __device__ constexpr int tile_tw_fill_chunks() {  // steps per thread (rounded up)
@@ -235,6 +264,15 @@ __host__ __device__ constexpr int tile_tw_fill_chunk(uint32_t tid, int k) {
   constexpr uint32_t chunks = 2u << LOG_R, threads = 1u << (LOG_R + LOG_T - 2);
   const uint32_t j = tid + (uint32_t)k * threads;
   return ((uint32_t)(k + 1) * threads <= chunks || j < chunks) ? (int)j : -1;
+}
+
+// WHERE THE OUTPUTS GO.  Position i of the DIF output holds frequency k = bitrev(i).  The last group's elements are i = ibase | h
+// with bits 0 and 1 of ibase clear, and bit reversal carries those two bits to the top: k_h = k_0 + tile_out_k_step(h), k_0 the
+// frequency of h = 0.  A thread reverses one index; the other three rows lie a wave-uniform distance behind it, which the scalar unit
+// scales by the launch's row stride once.
+template <int LOG_R>
+__host__ __device__ constexpr uint32_t tile_out_k_step(int h) {
+  return ((uint32_t)(h & 1) << (LOG_R - 1)) | ((uint32_t)(h >> 1) << (LOG_R - 2));
 }
 
 // Register group g: fetch 4 elements (global memory for g == 0, LDS otherwise), do its butterfly levels,
@@ -286,12 +324,16 @@ __device__ __forceinline__ void ntt_group(const NttPassArgs& a, uint4* lds, Tile
   constexpr int qhi = LOG_R - 1 - 2 * g;
   constexpr bool TWL = tile_tw_in_lds<LOG_R, LOG_T>();
   auto tw_needed = [](int b) constexpr { return tile_tw_needed<LOG_R, g>(b); };
-  auto tw_load = [&](int b) {
-    const uint32_t ex = tile_tw_exponent<LOG_R, g>(b, th.ibase);
+  auto tw_load = [&](auto bc) {  // butterfly b as an integral_constant: which form its address takes is known at compile time
+    constexpr int b = decltype(bc)::value;
     if constexpr (TWL) {
-      const uint4* tw = lds + (2u << (LOG_R + LOG_T));  // the table region behind the tile image
-      const uint32_t o = tw_lds_slot(ex, 0);            // the other chunks: one XOR each (tw_lds_slot(ex, c) == o ^ c)
-      const uint4 c0 = tw[o], c1 = tw[o ^ 1u], c2 = tw[o ^ 2u], c3 = tw[o ^ 3u];
+      const char* tw = reinterpret_cast<const char*>(lds + (2u << (LOG_R + LOG_T)));  // the table region behind the tile image
+      // tile_tw_byte(b, ibase, c) from the level's one address (tile_tw_level, tile_tw_read).  The empty asm keeps the compiler from
+      // merging the pair's key XOR into each chunk's address anew (four instructions instead of one).
+      uint32_t at = tile_tw_level<LOG_R, g, b>(th.ibase);
+      if constexpr (tile_tw_keyed<LOG_R, g, b>()) asm("" : "+v"(at));
+      auto chunk = [&](uint32_t c) { return *reinterpret_cast<const uint4*>(tw + tile_tw_read<LOG_R, g, b>(at, th.ibase, c)); };
+      const uint4 c0 = chunk(0), c1 = chunk(1), c2 = chunk(2), c3 = chunk(3);
       fp2 r;
       r.w.v[0] = c0.x; r.w.v[1] = c0.y; r.w.v[2] = c0.z; r.w.v[3] = c0.w;
       r.w.v[4] = c1.x; r.w.v[5] = c1.y; r.w.v[6] = c1.z; r.w.v[7] = c1.w;
@@ -299,7 +341,7 @@ __device__ __forceinline__ void ntt_group(const NttPassArgs& a, uint4* lds, Tile
       r.w128.v[4] = c3.x; r.w128.v[5] = c3.y; r.w128.v[6] = c3.z; r.w128.v[7] = c3.w;
       return r;
     } else {
-      return fp2_load(a.wR + ex);
+      return fp2_load(a.wR + tile_tw_exponent<LOG_R, g>(b, th.ibase));
     }
   };
   // one twiddle is always in flight: the first is requested before the elements are fetched, the next before the current
@@ -328,9 +370,9 @@ __device__ __forceinline__ void ntt_group(const NttPassArgs& a, uint4* lds, Tile
       if (j1 >= 0) tw[tw_lds_slot((uint32_t)j1 >> 2, (uint32_t)j1 & 3u)] = tw_fill1;
     }
     __syncthreads();
-    if constexpr (first_tw < 4) tw_cur = tw_load(first_tw);
+    if constexpr (first_tw < 4) tw_cur = tw_load(std::integral_constant<int, first_tw>{});
   };
-  if constexpr (first_tw < 4 && !(TWL && g == 0)) tw_cur = tw_load(first_tw);
+  if constexpr (first_tw < 4 && !(TWL && g == 0)) tw_cur = tw_load(std::integral_constant<int, first_tw>{});
 
   // ---- zero-padded source whose non-zero part ends inside the first quarter of the rows (the 8x low-degree extension:
   // rows i >= R / 8 of every column are zero): this thread's elements 1..3 are zero, so the group's two levels are
@@ -349,7 +391,7 @@ __device__ __forceinline__ void ntt_group(const NttPassArgs& a, uint4* lds, Tile
       }
       if (FP_ANY(in)) {  // wave-uniform
         if constexpr (!TWL) x0 = fp_load(a.src + th.sbase + (in ? off : 0));
-        const fp2 tw_b = tw_load(2), tw_c = tw_load(3);  // tw_cur holds butterfly 0's
+        const fp2 tw_b = tw_load(std::integral_constant<int, 2>{}), tw_c = tw_load(std::integral_constant<int, 3>{});  // tw_cur holds butterfly 0's
 #pragma unroll
         for (int w = 0; w < 8; ++w) x0.v[w] = in ? x0.v[w] : 0u;
         th.x[0] = x0;
@@ -379,8 +421,9 @@ __device__ __forceinline__ void ntt_group(const NttPassArgs& a, uint4* lds, Tile
     } else {
 #pragma unroll
       for (int h = 0; h < 4; ++h) {
-        const uint32_t i = th.ibase | ((uint32_t)h << beta);
-        th.x[h] = LAST ? fp_load(a.src + th.gbase + i) : fp_load(a.src + th.gbase + ((uint64_t)i << a.log_S));
+        // the rows of h = 1..3 lie a wave-uniform (h << beta) << log_S behind the thread's first
+        th.x[h] = LAST ? fp_load(a.src + th.gbase + (th.ibase | ((uint32_t)h << beta)))
+                       : fp_load(a.src + th.gbase + ((uint64_t)th.ibase << a.log_S) + ((uint64_t)((uint32_t)h << beta) << a.log_S));
       }
       // in the block of the element loads: the copy's wait then counts exactly these eight requests behind the table's
       if constexpr (TWL) tw_fill_finish();
@@ -400,7 +443,7 @@ __device__ __forceinline__ void ntt_group(const NttPassArgs& a, uint4* lds, Tile
       constexpr int hl = lb == 1 ? pr : 2 * pr;  // lower element of the pair
       constexpr int hh = hl | (1 << lb);
       constexpr int nxt = (b < 1 && tw_needed(1)) ? 1 : (b < 2 && tw_needed(2)) ? 2 : (b < 3 && tw_needed(3)) ? 3 : 4;
-      if constexpr (tw_needed(b) && nxt < 4) tw_nxt = tw_load(nxt);
+      if constexpr (tw_needed(b) && nxt < 4) tw_nxt = tw_load(std::integral_constant<int, nxt>{});
       const fp s = fp_add(th.x[hl], th.x[hh]);
       fp d = fp_sub(th.x[hl], th.x[hh]);
       if constexpr (tw_needed(b)) {
@@ -455,9 +498,8 @@ __device__ __forceinline__ void ntt_pass_body(const NttPassArgs& a) {
   // once, or two, cost a wave per SIMD (106 / 102 VGPRs) and measured slower on single vectors and on 2^24.
   fp itw[4];
   auto itw_load = [&](int h) {
-    const uint32_t i = tile_ibase<LOG_R, LOG_T, G - 1>(tid) | (uint32_t)h;  // the last group's element index (beta = 0)
-    const uint32_t k = __brev(i) >> (32 - LOG_R);
-    return fp_load(a.tw2 + ((uint64_t)k << a.log_S) + th.j2);
+    const uint32_t k0 = __brev(tile_ibase<LOG_R, LOG_T, G - 1>(tid)) >> (32 - LOG_R);  // the last group's h = 0 (beta = 0)
+    return fp_load(a.tw2 + ((uint64_t)k0 << a.log_S) + th.j2 + ((uint64_t)tile_out_k_step<LOG_R>(h) << a.log_S));
   };
   auto itw_request = [&]() {
     if (!LAST && a.tw2) itw[0] = itw_load(0);
@@ -489,19 +531,19 @@ __device__ __forceinline__ void ntt_pass_body(const NttPassArgs& a) {
 
   // ---- store: position i of the DIF output holds frequency k = bitrev(i) ----------------------------
   if (!th.active) return;
+  const uint32_t k0 = __brev(th.ibase) >> (32 - LOG_R);  // the last group's local bits sit at position 0: k of h is k0 + step(h)
 #pragma unroll
   for (int h = 0; h < 4; ++h) {
-    const uint32_t i = th.ibase | (uint32_t)h;  // the last group's local bits sit at position 0
-    const uint32_t k = __brev(i) >> (32 - LOG_R);
+    const uint32_t step = tile_out_k_step<LOG_R>(h);
     if (LAST) {
       fp v = th.x[h];
       if (a.scale) v = fp_mul(v, fp_load(a.scale));
-      fp_store(a.dst + th.obase + ((uint64_t)k << a.log_P), v);
+      fp_store(a.dst + th.obase + ((uint64_t)k0 << a.log_P) + ((uint64_t)step << a.log_P), v);
     } else {
       if (a.tw2 && h + 1 < 4) itw[h + 1] = itw_load(h + 1);
-      const fp tw = a.tw2 ? itw[h] : tw_lookup(a, th.j2 * k);
+      const fp tw = a.tw2 ? itw[h] : tw_lookup(a, th.j2 * (k0 + step));
       fp v = fp_mul(th.x[h], tw);
-      fp_store(a.dst + th.gbase + ((uint64_t)k << a.log_S), v);
+      fp_store(a.dst + th.gbase + ((uint64_t)k0 << a.log_S) + ((uint64_t)step << a.log_S), v);
     }
   }
 }
