@@ -15,7 +15,8 @@
 //   f64_canon(a)     = a mod p for any 64-bit a (two products: no bound on a / p is assumed, p may be 3).
 // On the host the products are unsigned __int128; on the device __umul64hi and 64-bit products, which compile to v_mad_u64_u32
 // chains.  Everything is __host__ __device__; the host builds the constants (f64_mod_init) and checks roots (f64_pow) with the same
-// code.  tests/test_ntt64_host.py pins every function against Python ints.
+// code.  tests/test_ntt64_host.py pins every function against Python ints; tests/test_modarith_host.py (host compile) and
+// tests/test_gpu_modarith.py (device compile, __umul64hi) pin each one elementwise on every operand class named above.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

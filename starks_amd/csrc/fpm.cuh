@@ -15,7 +15,8 @@
 //   fpm_canon(a)     = a mod p for any 256-bit a (two products: no bound on a / p is assumed, p may be 3).
 // All of it is plain C++: the 32 x 32 + 64-bit steps are written as uint64_t expressions that compile to v_mad_u64_u32.
 // Everything is __host__ __device__; the host builds the constants (fpm_mod_init) and checks roots (fpm_pow) with the same code.
-// tests/test_modntt_host.py pins every function against Python ints for ten moduli.
+// tests/test_modntt_host.py pins every function against Python ints for ten moduli; tests/test_modarith_host.py (host compile) and
+// tests/test_gpu_modarith.py (device compile) pin each one elementwise for thirteen, on every operand class named above.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
